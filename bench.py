@@ -2,6 +2,13 @@
 """Benchmark: encode+decode GB/s (device-resident) on BASELINE.json's metric workload.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload volume|image] [--padding P]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` ...).  ``--dump-outputs DIR`` also writes
+what the last timed step computed (``dump_outputs``).  Everything else -- the lossless round-trip
+gate, per-direction event timing and the roofline, the pinned-host end-to-end leg, the CPU
+baselines, the C4 leg at N > 1 -- runs only with ``--full``.
 
 One step = one fused encode pass + one fused decode pass over the whole batch (volume: the
 512^3 uint16 volume as 512 tiles of 64^3, BASELINE config C3; image: 1024 tiles of 256^2
@@ -56,7 +63,62 @@ def parse():
     ap.add_argument('--e2e-chunk', type=int, default=32, help='tiles per H2D/D2H copy in the end-to-end leg')
     ap.add_argument('--no-e2e', action='store_true', help='skip the pinned-host end-to-end leg')
     ap.add_argument('--stream-tiles', type=int, default=0, help='stream workload: chunks per GPU (0 = 512)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline: the lossless gate, per-direction timing and '
+                         'roofline, the end-to-end host leg, the CPU baselines, the C4 leg at N > 1')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
+
+
+DUMP_BUDGET = 48 << 20  # bytes --dump-outputs writes in all, array data (headers aside)
+DUMP_SEED = 20240
+
+
+def dump_index(numel, keep, i):
+    """The flat element indices --dump-outputs keeps of its ``i``-th array when the array has more
+    than ``keep`` elements: a fixed seeded draw, sorted, duplicates dropped; None = every element."""
+    if keep >= numel:
+        return None
+    return np.unique(np.random.default_rng(DUMP_SEED + i).integers(0, numel, size=keep, dtype=np.int64))
+
+
+def dump_layout(sizes):
+    """``sizes`` = [(elements, torch dtype)] of the arrays ``dump_outputs`` is given -> [(numpy dtype
+    written, elements kept)]: float32 where it holds every value of the array's dtype exactly
+    (8 / 16-bit integers, float32), float64 for the rest; each array keeps its share of
+    DUMP_BUDGET in proportion to its size."""
+    wide = [np.float32 if dt.itemsize <= 2 or dt == torch.float32 else np.float64 for _, dt in sizes]
+    cost = sum(n * np.dtype(w).itemsize for (n, _), w in zip(sizes, wide))
+    scale = min(1.0, DUMP_BUDGET / max(1, cost))
+    return [(w, n if scale == 1.0 else max(1, int(n * scale))) for (n, _), w in zip(sizes, wide)]
+
+
+_SAME_BITS = {torch.uint16: (torch.int16, np.uint16), torch.uint32: (torch.int32, np.uint32)}
+
+
+def dump_outputs(path, arrays):
+    """Write the outputs of the last timed step -- ``arrays`` = [(name, tensor)], the tensors a caller
+    of the timed path receives -- as ``path/<name>.npy``.  An array within its share of
+    DUMP_BUDGET is written whole, in its own shape; of a larger one the elements ``dump_index``
+    draws, as a 1-d array.  Inputs and draw are seeded, so two builds write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    if any(t.is_cuda for _, t in arrays):
+        torch.cuda.synchronize()
+    layout = dump_layout([(t.numel(), t.dtype) for _, t in arrays])
+    for i, ((name, t), (wide, keep)) in enumerate(zip(arrays, layout)):
+        idx = dump_index(t.numel(), keep, i)
+        signed, unsigned = _SAME_BITS.get(t.dtype, (t.dtype, None))  # gather on the bits: same values
+        t = t.contiguous().view(signed)
+        if idx is not None:
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        if unsigned is not None:
+            a = a.view(unsigned)
+        np.save(os.path.join(path, name + '.npy'), a.astype(wide))
 
 
 def synthetic(spec, seed):
@@ -419,11 +481,13 @@ def main():
     def decode():
         _nd.fused_decode_into(lowres, maps, dims, predictor, coder, rec, ndim, workspace=ws)
 
-    # correctness gate before timing: lossless round trip of the whole batch
+    # one untimed pair before the warm-up loads the code objects (as every run always did);
+    # --full makes it the correctness gate: lossless round trip of the whole batch
     encode()
     decode()
-    torch.cuda.synchronize()
-    assert torch.equal(rec, hi), 'round trip is not lossless'
+    if args.full:
+        torch.cuda.synchronize()
+        assert torch.equal(rec, hi), 'round trip is not lossless'
 
     for _ in range(args.warmup):
         encode()
@@ -449,28 +513,36 @@ def main():
             run_enc()
             run_dec()
         torch.cuda.synchronize()
-        assert torch.equal(rec, hi), 'graph replay round trip is not lossless'
+        if args.full:
+            assert torch.equal(rec, hi), 'graph replay round trip is not lossless'
     elapsed = timed_steps(run_enc, run_dec, args.steps, dist)
-    t_enc, t_dec = direction_times(run_enc, run_dec, max(args.steps, 10), dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [('lowres', lowres), *((f'map{i}', m) for i, m in enumerate(maps)),
+                                         ('restored', rec)])
 
     raw = hi.numel() * hi.element_size()           # raw highres bytes per rank per step
     value = raw * world * args.steps / elapsed / 1e9
     ms_per_step = elapsed / args.steps * 1e3
-    # algorithmic HBM bytes per launch: read + write of the raw volume
-    algo = 2 * raw
-    dominant, t_dom = ('encode', t_enc) if t_enc >= t_dec else ('decode', t_dec)
-    achieved = algo / t_dom / 1e9
-    traffic = load_traffic(args.workload, args.padding, dominant)
 
-    c4 = c4_strong(kom, hi, predictor, ndim, dist, world, ws) if dist else None
+    roofline = c4 = e2e = base = None
+    if args.full:
+        t_enc, t_dec = direction_times(run_enc, run_dec, max(args.steps, 10), dist)
+        # algorithmic HBM bytes per launch: read + write of the raw volume
+        algo = 2 * raw
+        dominant, t_dom = ('encode', t_enc) if t_enc >= t_dec else ('decode', t_dec)
+        achieved = algo / t_dom / 1e9
+        traffic = load_traffic(args.workload, args.padding, dominant)
+        roofline = {'bound': 'hbm', 'kernel': f'{kernel_name(ndim, args.padding, dominant, spec["dtype"] == np.uint8)} {dominant}',
+                    'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                    'frac': round(achieved / HBM_PEAK_GBS, 4),
+                    'traffic': traffic, 'algorithmic_bytes_per_launch': algo}
 
-    e2e = None
-    if world == 1 and not args.no_e2e:
-        e2e = e2e_leg(kom, host, predictor, ndim, args.e2e_chunk)
-
-    base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        base = cpu_baseline(spec, host, args.padding, args.cpu_tiles)
+        if dist:
+            c4 = c4_strong(kom, hi, predictor, ndim, dist, world, ws)
+        if world == 1 and not args.no_e2e:
+            e2e = e2e_leg(kom, host, predictor, ndim, args.e2e_chunk)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            base = cpu_baseline(spec, host, args.padding, args.cpu_tiles)
 
     if rank == 0:
         line = {
@@ -484,15 +556,15 @@ def main():
                        'parallelism': f'tiles sharded, dp{world}' if world > 1 else 'single GPU',
                        'value_is': 'whole-job aggregate: raw highres bytes coded by all ranks / wall time '
                                    '(weak scaling: every rank codes its own full batch; value_per_gpu = value / n_gpus)'},
-            'ms_encode': round(t_enc * 1e3, 5), 'ms_decode': round(t_dec * 1e3, 5),
             'dist': dist_info(dist, world),
             'launch': 'hipGraph replay (one graph per direction)' if args.graph else 'eager (one ctypes launch per direction)',
-            'roofline': {'bound': 'hbm', 'kernel': f'{kernel_name(ndim, args.padding, dominant, spec["dtype"] == np.uint8)} {dominant}',
-                         'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': round(achieved / HBM_PEAK_GBS, 4),
-                         'traffic': traffic, 'algorithmic_bytes_per_launch': algo},
-            'cpu_baseline': base,
+            'full': args.full,
         }
+        if args.full:
+            line.update({'ms_encode': round(t_enc * 1e3, 5), 'ms_decode': round(t_dec * 1e3, 5),
+                         'roofline': roofline, 'cpu_baseline': base})
+        if args.dump_outputs:
+            line['dumped_outputs'] = args.dump_outputs
         if e2e:
             line['e2e_host'] = e2e
         if c4:
@@ -500,6 +572,69 @@ def main():
         print(json.dumps(line), flush=True)
     if dist:
         dist.destroy_process_group()
+
+
+def stream_roofline(kom, src, n, predictor):
+    """Kernel roofline of the C5 codec device-resident (the uint32 one-pass kernel,
+    kmp_codec_wave3d32.hip) on a 64-chunk slice."""
+    from kompressor_amd import _nd
+    k = min(64, n)
+    d_hi = src[:k].cuda().view(torch.uint32)
+    coder = _nd.NATURAL_CODER[torch.uint32]
+    d_lo, d_maps, d_dims = _nd._alloc_encoded(d_hi, coder, 3)
+    d_rec = torch.empty_like(d_hi)
+    ws = torch.empty(max(1, _nd.workspace_bytes(d_hi, predictor, 3)), dtype=torch.uint8, device='cuda')
+    enc = lambda: _nd.fused_encode_into(d_hi, predictor, coder, d_lo, d_maps, 3, workspace=ws)  # noqa: E731
+    dec = lambda: _nd.fused_decode_into(d_lo, d_maps, d_dims, predictor, coder, d_rec, 3, workspace=ws)  # noqa: E731
+    enc()
+    kname_enc = kom._lib.lib.kmp_last_launch().decode()
+    dec()
+    kname_dec = kom._lib.lib.kmp_last_launch().decode()
+    k_enc, k_dec = direction_times(enc, dec, 5, None)
+    assert torch.equal(d_rec, d_hi)
+    kraw = d_hi.numel() * 4
+    dominant, t_dom = ('encode', k_enc) if k_enc >= k_dec else ('decode', k_dec)
+    achieved = 2 * kraw / t_dom / 1e9
+    return {'bound': 'hbm', 'kernel': kname_enc if dominant == 'encode' else kname_dec,
+            'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+            'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': None,
+            'algorithmic_bytes_per_launch': 2 * kraw,
+            'device_resident_ms': {'encode': round(k_enc * 1e3, 4), 'decode': round(k_dec * 1e3, 4),
+                                   'chunks': k}}
+
+
+def stream_cpu_baseline(src, n, padding):
+    """The same two restatements as the C3 / C2 lines, on the uint32 bit patterns."""
+    from oracle import volume as OV, predictors as OP, torch_cpu as TC
+    host32 = src.numpy().view(np.uint32)
+    pf = OP.mean_predictions_fn(padding, 3)
+    nn, nt = min(n, 2), min(n, 8)
+    out = {}
+
+    def numpy_round():
+        lo_o, enc_o = OV.encode(pf, OV.encode_values_uint32, host32[:nn], padding=padding)
+        out['np'] = OV.decode(pf, OV.decode_values_uint32, lo_o, enc_o, padding=padding)
+
+    def torch_round():
+        lo_t, enc_t = TC.encode(host32[:nt], padding, 3)
+        out['torch'] = TC.decode(lo_t, enc_t, padding, 3)
+
+    threads, how = host_cores()
+    prev = torch.get_num_threads()
+    torch.set_num_threads(threads)
+    try:
+        r_t, t_t = _median_rate(torch_round, host32[:nt].nbytes)
+    finally:
+        torch.set_num_threads(prev)
+    assert np.array_equal(out['torch'], host32[:nt])
+    r_n, t_n = _median_rate(numpy_round, host32[:nn].nbytes)
+    assert np.array_equal(out['np'], host32[:nn])
+    return {'value': round(r_t, 4), 'unit': 'GB/s', 'cores': threads, 'kind': 'port',
+            'sample': f'{nt} of {n} chunks of 128^3: torch-CPU restatement (oracle/torch_cpu.py, uint32 '
+                      f'bit-cast) on {threads} threads ({how}), 1 warm-up + median of 5, {t_t:.3f} s/round',
+            'single_thread_numpy': {'value': round(r_n, 4), 'unit': 'GB/s', 'cores': 1, 'kind': 'port',
+                                    'sample': f'{nn} of {n} chunks, numpy restatement (oracle/), 1 thread, '
+                                              f'1 warm-up + median of 5, {t_n:.3f} s/round'}}
 
 
 def main_stream(args):
@@ -512,7 +647,6 @@ def main_stream(args):
     spec['shape'] = (n, *spec['shape'][1:])
     world, rank, dist = init_dist()
     import kompressor_amd as kom
-    from kompressor_amd import _nd
     predictor = kom.MeanPredictor(args.padding, 3)
     chunk_shape = spec['shape'][1:]
     # synthetic float32 chunks: 16 distinct random chunks tiled over the batch (the codec's cost
@@ -535,7 +669,8 @@ def main_stream(args):
         return t
 
     step()
-    assert torch.equal(out.view(torch.uint32), src.view(torch.uint32)), 'C5 round trip is not lossless'
+    if args.full:
+        assert torch.equal(out.view(torch.uint32), src.view(torch.uint32)), 'C5 round trip is not lossless'
     for _ in range(args.warmup):
         step()
     if dist:
@@ -558,59 +693,15 @@ def main_stream(args):
         elapsed, t_enc, t_dec = tt.tolist()
     raw = src.numel() * 4
 
-    # kernel roofline of the same codec device-resident (the uint32 one-pass kernel,
-    # kmp_codec_wave3d32.hip) on a 64-chunk slice
-    k = min(64, n)
-    d_hi = src[:k].cuda().view(torch.uint32)
-    coder = _nd.NATURAL_CODER[torch.uint32]
-    d_lo, d_maps, d_dims = _nd._alloc_encoded(d_hi, coder, 3)
-    d_rec = torch.empty_like(d_hi)
-    ws = torch.empty(max(1, _nd.workspace_bytes(d_hi, predictor, 3)), dtype=torch.uint8, device='cuda')
-    enc = lambda: _nd.fused_encode_into(d_hi, predictor, coder, d_lo, d_maps, 3, workspace=ws)  # noqa: E731
-    dec = lambda: _nd.fused_decode_into(d_lo, d_maps, d_dims, predictor, coder, d_rec, 3, workspace=ws)  # noqa: E731
-    enc()
-    kname_enc = kom._lib.lib.kmp_last_launch().decode()
-    dec()
-    kname_dec = kom._lib.lib.kmp_last_launch().decode()
-    k_enc, k_dec = direction_times(enc, dec, 5, None)
-    assert torch.equal(d_rec, d_hi)
-    kraw = d_hi.numel() * 4
-    dominant, t_dom = ('encode', k_enc) if k_enc >= k_dec else ('decode', k_dec)
-    achieved = 2 * kraw / t_dom / 1e9
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [('lowres', lo), *((f'map{i}', m) for i, m in enumerate(maps)),
+                                         ('restored', out)])
 
-    base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        # the same two restatements as the C3 / C2 lines, on the uint32 bit patterns
-        from oracle import volume as OV, predictors as OP, torch_cpu as TC
-        host32 = src.numpy().view(np.uint32)
-        pf = OP.mean_predictions_fn(args.padding, 3)
-        nn, nt = min(n, 2), min(n, 8)
-        out = {}
-
-        def numpy_round():
-            lo_o, enc_o = OV.encode(pf, OV.encode_values_uint32, host32[:nn], padding=args.padding)
-            out['np'] = OV.decode(pf, OV.decode_values_uint32, lo_o, enc_o, padding=args.padding)
-
-        def torch_round():
-            lo_t, enc_t = TC.encode(host32[:nt], args.padding, 3)
-            out['torch'] = TC.decode(lo_t, enc_t, args.padding, 3)
-
-        threads, how = host_cores()
-        prev = torch.get_num_threads()
-        torch.set_num_threads(threads)
-        try:
-            r_t, t_t = _median_rate(torch_round, host32[:nt].nbytes)
-        finally:
-            torch.set_num_threads(prev)
-        assert np.array_equal(out['torch'], host32[:nt])
-        r_n, t_n = _median_rate(numpy_round, host32[:nn].nbytes)
-        assert np.array_equal(out['np'], host32[:nn])
-        base = {'value': round(r_t, 4), 'unit': 'GB/s', 'cores': threads, 'kind': 'port',
-                'sample': f'{nt} of {n} chunks of 128^3: torch-CPU restatement (oracle/torch_cpu.py, uint32 '
-                          f'bit-cast) on {threads} threads ({how}), 1 warm-up + median of 5, {t_t:.3f} s/round',
-                'single_thread_numpy': {'value': round(r_n, 4), 'unit': 'GB/s', 'cores': 1, 'kind': 'port',
-                                        'sample': f'{nn} of {n} chunks, numpy restatement (oracle/), 1 thread, '
-                                                  f'1 warm-up + median of 5, {t_n:.3f} s/round'}}
+    roofline = base = None
+    if args.full:
+        roofline = stream_roofline(kom, src, n, predictor)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            base = stream_cpu_baseline(src, n, args.padding)
     if rank == 0:
         line = {
             'metric': spec['metric'], 'value': round(raw * world * args.steps / elapsed / 1e9, 3), 'unit': 'GB/s',
@@ -624,17 +715,15 @@ def main_stream(args):
                                if ts.zero_copy else 'copy pipeline (3 streams, 1 chunk per copy)',
                        'parallelism': f'chunks sharded, dp{world}' if world > 1 else 'single GPU'},
             'ms_encode': round(t_enc / args.steps * 1e3, 3), 'ms_decode': round(t_dec / args.steps * 1e3, 3),
-            'roofline': {'bound': 'hbm', 'kernel': kname_enc if dominant == 'encode' else kname_dec,
-                         'achieved': round(achieved, 2), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                         'frac': round(achieved / HBM_PEAK_GBS, 4), 'traffic': None,
-                         'algorithmic_bytes_per_launch': 2 * kraw,
-                         'device_resident_ms': {'encode': round(k_enc * 1e3, 4), 'decode': round(k_dec * 1e3, 4),
-                                                'chunks': k}},
             'dist': dist_info(dist, world),
             'link': {'h2d_plus_d2h_bytes_per_step': 4 * raw,
                      'note': 'each direction moves the raw volume host->device and its coded form back'},
-            'cpu_baseline': base,
+            'full': args.full,
         }
+        if args.full:
+            line.update({'roofline': roofline, 'cpu_baseline': base})
+        if args.dump_outputs:
+            line['dumped_outputs'] = args.dump_outputs
         print(json.dumps(line), flush=True)
     if dist:
         dist.destroy_process_group()

@@ -49,7 +49,10 @@ def test_launch_command_starts_n_gloo_ranks(tmp_path):
         dist.init_process_group('gloo')
         t = torch.ones(1)
         dist.all_reduce(t)
-        print(f"rank={dist.get_rank()} world={dist.get_world_size()} sum={int(t.item())} argv={sys.argv[1:]}", flush=True)
+        # one write() per line: the ranks share the pipe, and an unbuffered print() writes the text
+        # and its newline separately, so two ranks' lines could run together
+        line = f"rank={dist.get_rank()} world={dist.get_world_size()} sum={int(t.item())} argv={sys.argv[1:]}"
+        os.write(1, (line + chr(10)).encode())
         dist.destroy_process_group()
     '''))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}

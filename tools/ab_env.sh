@@ -7,7 +7,7 @@ O=$1; VAR=$2; VALS=$3; REPS=${4:-2}; shift 4
 mkdir -p $(dirname $O)
 for r in $(seq $REPS); do
   for v in $VALS; do
-    line=$(env $VAR=$v timeout -k 10 200 python bench.py --no-cpu-baseline --no-e2e "$@" 2>/dev/null | tail -1) || exit 1
+    line=$(env $VAR=$v timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-e2e "$@" 2>/dev/null | tail -1) || exit 1
     echo "$VAR=$v $(echo "$line" | python3 -c 'import sys, json; d = json.loads(sys.stdin.read()); print(d["value"], d["ms_encode"], d["ms_decode"])')" | tee -a $O
   done
 done

@@ -12,7 +12,7 @@ mkdir -p $O
 step() { local name=$1; shift; timeout -k 10 "$@" > $O/$name.log 2>&1; local rc=$?; echo "[$name] rc=$rc"; return $rc; }
 bash tools/gpu_round.sh ${1:-final} && \
 step debug_parity 600 env KMP_DEBUG=1 python -u -m pytest tests/test_gpu_codec.py tests/test_gpu_linear.py tests/test_packing.py -m gpu -x -q --timeout 120 --timeout-method thread && \
-step bench_n2_gloo 300 env KMP_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 5 --warmup 2 --no-e2e
+step bench_n2_gloo 300 env KMP_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 5 --warmup 2 --no-e2e
 rc=$?
 tail -2 $O/debug_parity.log; tail -1 $O/bench_n2_gloo.log
 exit $rc
