@@ -198,6 +198,20 @@ int kmp_linear_predict_mfma(int32_t nsp, int32_t dtype, const void* padded_lowre
                             int64_t C, int32_t padding, const float* weights, const float* bias, void* preds_out,
                             float* preds_f32, kmp_stream_t stream);
 
+/* Exact second moments for a least-squares fit of the linear predictor: M = X^T X [Q, Q] int64
+   (row-major, overwritten), one row of X per cell of the UNPADDED highres [B, shape..., 1]:
+     X = [ features_from_lowres(pad_neighborhood(lowres_from_highres(pad_highres(h)), p), p)  (N columns),
+           targets_from_highres(pad_highres(h))                                             (K = 19 / 5),
+           1 ],   Q = N + K + 1
+   (volume/utils.py:37-74,199-218,226-237; image/utils.py:38-49,121-137,146-156) -- the cells and
+   feature windows ``encode`` evaluates the predictor on.  uint8 / uint16 samples, C == 1, volumes
+   with padding 0 or 1, images with padding 0, 1 or 2 (else KMP_ERR_UNSUPPORTED); at most 2^31 - 1
+   cells per call (else KMP_ERR_ARG; moments add, so split the batch).  ``workspace`` holds
+   kmp_linear_moments_workspace_bytes() bytes (0 for an unsupported configuration), 8-byte aligned. */
+size_t kmp_linear_moments_workspace_bytes(int32_t nsp, int32_t dtype, int32_t padding);
+int kmp_linear_moments(int32_t nsp, int32_t dtype, const void* highres, int64_t B, const int64_t shape[3],
+                       int64_t C, int32_t padding, int64_t* moments, void* workspace, kmp_stream_t stream);
+
 /* jnp.pad on the spatial axes (volume/utils.py:213-260, image/utils.py:132-178):
    mode 0 = 'symmetric', 1 = 'reflect'.  Negative pads crop (== trim, volume/utils.py:263-276). */
 int kmp_pad(int32_t nsp, int32_t dtype, const void* in, int64_t B, const int64_t shape[3], int64_t C,

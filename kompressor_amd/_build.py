@@ -39,7 +39,10 @@ def _headers_mtime():
 # (the results) per MFMA, 256 VALU instructions per wave step of kmp_codec_linear3m.hip
 FILE_FLAGS = {'kmp_codec_linear3m.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'],
               'kmp_codec_linear3pm.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'],
-              'kmp_linear.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
+              'kmp_linear.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'],
+              # kmp_fit.hip: the i32 accumulators are flushed from VGPRs; 248 registers instead of 348
+              # for uint16 volumes with padding 1, so two workgroups share a CU
+              'kmp_fit.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
 
 
 def _compile(src, hdr_mtime, verbose, debug=False):

@@ -88,6 +88,8 @@ _PROTOS = {
     'kmp_mean_predict_maps_typed': (ctypes.c_int, [_i32, _i32, _i32, _vp, _i64, _i64p, _i64, _i32, _vpp, _vp]),
     'kmp_linear_predict': (ctypes.c_int, [_i32, _i32, _vp, _i64, _i64p, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     'kmp_linear_predict_mfma': (ctypes.c_int, [_i32, _i32, _vp, _i64, _i64p, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'kmp_linear_moments_workspace_bytes': (ctypes.c_size_t, [_i32, _i32, _i32]),
+    'kmp_linear_moments': (ctypes.c_int, [_i32, _i32, _vp, _i64, _i64p, _i64, _i32, _vp, _vp, _vp]),
     'kmp_pad': (ctypes.c_int, [_i32, _i32, _vp, _i64, _i64p, _i64, _i64p, _i64p, _i32, _vp, _vp]),
     'kmp_copy_box': (ctypes.c_int, [_i32, _i32, _vp, _i64p, _i64p, _i32, _vp, _i64p, _i64p, _i64, _i64, _i64p,
                                     _vp]),

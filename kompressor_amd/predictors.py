@@ -17,7 +17,7 @@ import torch
 
 from . import _device as dev
 from . import _lib
-from ._nd import d_mean_predict_maps, d_maps_from_predictions, NPRED, _sp, _ch, _C
+from ._nd import d_mean_predict_maps, d_maps_from_predictions, NPRED, _sp, _ch, _C, _require
 from ._lib import check, lib
 
 
@@ -165,3 +165,130 @@ class LinearPredictor:
     def __repr__(self):
         ar = '' if self.arith == 'auto' else f", arith='{self.arith}'"
         return f'LinearPredictor(padding={self.padding}, ndim={self.ndim}{ar})'
+
+    @classmethod
+    def from_moments(cls, moments, padding=0, ndim=3, arith='auto', ridge=0.0):
+        """The least-squares predictor of the data whose moments (:func:`linear_moments`, or a sum
+        of them) are ``moments``."""
+        _check_fit_config(padding, ndim)
+        w, b = solve_moments(moments, (2 * padding + 2) ** ndim, ridge=ridge)
+        return cls(w, b, padding, ndim, arith)
+
+    @classmethod
+    def fit(cls, highres, padding=0, ndim=3, arith='auto', ridge=0.0):
+        """Least-squares fit on ``highres`` (``[B, spatial..., 1]`` uint8 / uint16, numpy or CUDA
+        tensor), or on an iterable of such arrays: moments add, so a sample of tiles, or the chunks
+        of a volume too large for one call, fit as the sum of their moments.  The moments are
+        accumulated exactly on the GPU (kmp_fit.hip); the small solve is host float64."""
+        if isinstance(highres, (np.ndarray, torch.Tensor)):
+            highres = (highres,)
+        total = None
+        for h in highres:
+            m = linear_moments(h, padding, ndim)
+            total = m if total is None else total + m
+        if total is None:
+            raise ValueError('fit needs at least one array')
+        return cls.from_moments(total, padding, ndim, arith, ridge)
+
+
+# =============================================================================================
+# Fitting: exact data moments on the GPU, the small solve on the host
+# =============================================================================================
+
+FIT_MAX_PADDING = {3: 1, 2: 2}  # kmp_fit.hip: N = 216 (volumes, padding 2) needs a multi-pass schedule
+FIT_MAX_CELLS = 2 ** 31 - 1     # a uint16 sum of squares over more cells can pass 2^63
+
+
+def _check_fit_config(padding, ndim):
+    _require(ndim in (2, 3), 'ndim must be 2 (image) or 3 (volume)')
+    _require(isinstance(padding, int) and not isinstance(padding, bool), 'padding must be an int')
+    _require(0 <= padding <= FIT_MAX_PADDING[ndim],
+             f'linear_moments takes padding 0..{FIT_MAX_PADDING[ndim]} for ndim={ndim}')
+
+
+def _check_fit_input(highres, padding, ndim):
+    """Everything ``linear_moments`` refuses, checked before the device is touched."""
+    _check_fit_config(padding, ndim)
+    if isinstance(highres, torch.Tensor):
+        ok = highres.dtype in (torch.uint8, torch.uint16)
+    else:
+        highres = np.asarray(highres)
+        ok = highres.dtype in (np.dtype(np.uint8), np.dtype(np.uint16))
+    if not ok:
+        raise TypeError(f'linear_moments takes uint8 / uint16 samples, not {highres.dtype}')
+    shape = tuple(int(s) for s in highres.shape)
+    _require(len(shape) == ndim + 2, f'highres must be [B, {ndim} spatial dims, 1]')
+    _require(shape[-1] == 1, 'linear_moments takes single-channel data (C == 1)')
+    _require(shape[0] >= 1 and all(s >= 2 for s in shape[1:1 + ndim]), 'empty batch or spatial dim < 2')
+    cells = shape[0]
+    for s in shape[1:1 + ndim]:
+        cells *= s // 2  # == (s + (s + 1) % 2 - 1) // 2 cells of the padded dim
+    _require(cells <= FIT_MAX_CELLS, f'more than 2^31 - 1 cells in one call ({cells}): split the batch, moments add')
+    return highres
+
+
+def linear_moments(highres, padding=0, ndim=3):
+    """Exact second moments ``M = X^T X`` (numpy int64 ``[Q, Q]``, ``Q = N + K + 1``) of
+    ``X = [features, targets, 1]`` over every cell ``encode`` evaluates a predictor on:
+    ``features_from_lowres(pad_neighborhood(lowres_from_highres(pad_highres(h)), p), p)``
+    (``N = (2p+2)^ndim`` columns, z-major / y / x), ``targets_from_highres(pad_highres(h))``
+    (``K`` = 19 / 5, reference order) and the constant 1; ``M[Q-1, Q-1]`` is the cell count.
+    Integers, so exact, order-independent and additive over tiles, chunks and ranks.
+
+    ``highres``: ``[B, spatial..., 1]`` uint8 / uint16, numpy or CUDA tensor; volumes take padding
+    0 or 1, images 0, 1 or 2."""
+    highres = _check_fit_input(highres, padding, ndim)
+    t, _ = dev.to_device(highres)
+    n, k = (2 * padding + 2) ** ndim, NPRED[ndim]
+    q = n + k + 1
+    code = dev.dtype_code(t)
+    ws = dev.empty((lib.kmp_linear_moments_workspace_bytes(ndim, code, padding) // 8,), torch.int64)
+    out = dev.empty((q, q), torch.int64)
+    check(lib.kmp_linear_moments(ndim, code, t.data_ptr(), t.shape[0], _lib.i64x3(_sp(t.shape, ndim)), 1, padding,
+                                 out.data_ptr(), ws.data_ptr(), dev.stream()), 'linear_moments')
+    return out.cpu().numpy()
+
+
+def solve_moments(moments, n_features, ridge=0.0, round_bias=True, dtype=np.float32):
+    """``(W float32 [N, K], b float32 [K])`` minimising ``sum |F W + b - T|^2`` for the data whose
+    moments are ``moments`` (``[Q, Q]`` integers, columns: N features, K targets, 1).  Pure numpy.
+
+    The system is centred in exact integers (``n M_ij - s_i s_j``, Python ints: no cancellation),
+    then solved in float64 as the minimum-norm least-squares solution, so constant or
+    rank-deficient data give a defined result (zero weights along the null directions), never an
+    exception.  ``ridge`` adds ``ridge * trace / N`` to the diagonal.  ``b = mean_T - mean_F W``;
+    ``round_bias`` adds 0.5, so the predictor's truncating cast rounds to nearest.  ``dtype=float64``
+    returns the solution before its rounding to the predictor's float32 parameters."""
+    M = np.asarray(moments)
+    if M.ndim != 2 or M.shape[0] != M.shape[1]:
+        raise ValueError('moments must be a square [Q, Q] matrix')
+    N = int(n_features)
+    Q = M.shape[0]
+    K = Q - 1 - N
+    if N < 1 or K < 1:
+        raise ValueError(f'moments [{Q}, {Q}] hold no targets for {N} features')
+    if ridge < 0:
+        raise ValueError('ridge must be >= 0')
+    Mi = M.astype(object)  # Python ints: the centred entries reach 2^94
+    cnt = int(Mi[Q - 1, Q - 1])
+    if cnt <= 0:
+        raise ValueError('moments of no cells')
+    s = [int(v) for v in Mi[Q - 1, :Q - 1]]
+    NK = N + K
+    cen = np.empty((NK, NK), np.float64)
+    for i in range(NK):
+        for j in range(i, NK):
+            cen[i, j] = cen[j, i] = float(cnt * int(Mi[i, j]) - s[i] * s[j])
+    cen /= float(cnt) * float(cnt)  # covariances, in squared sample levels
+    cff, cft = cen[:N, :N].copy(), cen[:N, N:]
+    if ridge:
+        cff[np.diag_indices(N)] += ridge * np.trace(cff) / N
+    w = np.linalg.lstsq(cff, cft, rcond=None)[0]
+    mean = np.array([v / cnt for v in s], np.float64)
+    dt = np.dtype(dtype).type
+    # the bias on the coarser of the two grids b and b + 0.5 round to in ``dtype``, so both are
+    # representable and the rounded bias is the plain one plus exactly 0.5 (|b| < 2^23)
+    b64 = mean[N:] - mean[:N] @ w
+    q = np.maximum(np.spacing(np.abs(b64.astype(dt))), np.spacing(np.abs((b64 + 0.5).astype(dt)))).astype(np.float64)
+    b = (np.round(b64 / q) * q).astype(dt)
+    return w.astype(dt), (b + dt(0.5) if round_bias else b)
