@@ -1,4 +1,5 @@
-// kmp_codec.h -- internal interfaces between the fused-codec translation units.
+// kmp_codec.h -- internal interfaces between the fused-codec translation units: the request every
+// one-pass kernel family takes, one entry point per family, and the host checks they share.
 #pragma once
 
 #include "kmp_aggregate.h"
@@ -20,78 +21,110 @@ template <typename T>
 int linear_cells(const T* src, const int64_t* S, int mult, const Geo& g, int nsp, int64_t B, int64_t C,
                  const kmp_predictor* pred, const int64_t* cbegin, const int64_t* cext, T* cells, hipStream_t stream);
 
-// One-pass kernels (kmp_codec_fast3d.hip / kmp_codec_fast2d.hip).  Return KMP_ERR_UNSUPPORTED
-// (without touching anything) when the request is not eligible, so the caller falls back.
-template <typename T>
-int try_fast2d_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                      const MapPtrs& maps, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_fast2d_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                      const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_linear3pm_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                         const MapPtrs& maps, const kmp_region* region, void* ws, size_t ws_bytes,
-                         hipStream_t stream);
-template <typename T>
-int try_linear3pm_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                         const kmp_predictor* pred, T* hi, const kmp_region* region, void* ws, size_t ws_bytes,
-                         hipStream_t stream);
-template <typename T>
-int try_linear3m_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                        const MapPtrs& maps, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_linear3m_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                        const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_linear3d_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                        const MapPtrs& maps, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_linear3d_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                        const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_wave2d_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                      const MapPtrs& maps, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_wave2d_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                      const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_wave3d_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                      const MapPtrs& maps, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_wave3d_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                      const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_wave3dp_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                       const MapPtrs& maps, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_wave3dp_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                       const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_wave2dp_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                       const MapPtrs& maps, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_wave2dp_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                       const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_linear3dp_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                         const MapPtrs& maps, const kmp_region* region, void* ws, size_t ws_bytes,
-                         hipStream_t stream);
-template <typename T>
-int try_linear3dp_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                         const kmp_predictor* pred, T* hi, const kmp_region* region, void* ws, size_t ws_bytes,
-                         hipStream_t stream);
-template <typename T>
-int try_wave3d32_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                        const MapPtrs& maps, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_wave3d32_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                        const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream);
-template <typename T>
-int try_fast_encode(int nsp, const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                    const MapPtrs& maps, const kmp_region* region, void* ws, size_t ws_bytes, hipStream_t stream);
-template <typename T>
-int try_fast_decode(int nsp, const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                    const kmp_predictor* pred, T* hi, const kmp_region* region, void* ws, size_t ws_bytes,
-                    hipStream_t stream);
+// One encode (DEC = false) or decode (DEC = true) request of the fused codec.
+template <typename T, bool DEC>
+struct CodecCall {
+  int nsp;
+  const Geo& g;
+  int64_t B, C;
+  const kmp_predictor* pred;
+  const kmp_region* region;
+  const T* in;   // highres (encode) / lowres (decode)
+  T* out;        // lowres (encode) / highres (decode)
+  MapPtrs maps;  // written by encode, read by decode
+  void* ws;
+  size_t ws_bytes;
+  hipStream_t stream;
+};
+
+// One-pass kernel families, one per kmp_codec_<family>.hip.  Each returns KMP_ERR_UNSUPPORTED
+// (without touching anything) when the request is not eligible, and knows nothing of the others:
+// the order they are tried in is the table next to codec_encode / codec_decode
+// (kmp_codec_generic.hip).  Instantiated for uint8_t / uint16_t, wave3d32 for int32_t / uint32_t.
+template <typename T, bool DEC> int try_wave3d(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_wave3d32(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_wave3dp(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_fast3d(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_linear3d(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_linear3dp(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_linear3m(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_linear3pm(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_wave2d(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_wave2dp(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_fast2d(const CodecCall<T, DEC>& c);
+
+#define KMP_INST_FAMILY(F, T)                           \
+  template int F<T, false>(const CodecCall<T, false>&); \
+  template int F<T, true>(const CodecCall<T, true>&);
+#define KMP_INST_FAMILY_U8_U16(F) KMP_INST_FAMILY(F, uint8_t) KMP_INST_FAMILY(F, uint16_t)
+
+// ------------------------------------------------------------------------------------------
+// Host checks and argument filling the families share
+// ------------------------------------------------------------------------------------------
+
+// the region's span along axis ``a`` clamped to [0, E) (may come out empty: end <= begin)
+inline void region_clamp(const kmp_region* region, const Geo& g, int a, int64_t& begin, int64_t& end) {
+  begin = region->begin[a] < 0 ? 0 : region->begin[a];
+  end = region->end[a] > g.E[a] ? g.E[a] : region->end[a];
+}
+
+// A region may only restrict ``axis`` (0: the z slabs of a volume, 1: the row ranges of an image,
+// whose axis 0 is a dummy): [begin, end) is its clamped span; false when it restricts another axis
+// or is empty.  No region: the whole axis.
+inline bool region_span(const kmp_region* region, const Geo& g, int axis, int64_t& begin, int64_t& end) {
+  begin = 0;
+  end = g.E[axis];
+  if (!region) return true;
+  for (int a = 1; a < 3; ++a)
+    if (a != axis && (region->begin[a] > 0 || region->end[a] < g.E[a])) return false;
+  region_clamp(region, g, axis, begin, end);
+  return end > begin;
+}
+
+// highres aligned to ``hi_align`` bytes, lowres and the first ``nmaps`` maps to ``lo_align``
+template <typename T, bool DEC>
+inline bool ptrs_aligned(const CodecCall<T, DEC>& c, size_t hi_align, size_t lo_align, int nmaps) {
+  const void* hi = DEC ? (const void*)c.out : (const void*)c.in;
+  const void* lo = DEC ? (const void*)c.in : (const void*)c.out;
+  if (((uintptr_t)hi & (hi_align - 1)) || ((uintptr_t)lo & (lo_align - 1))) return false;
+  for (int k = 0; k < nmaps; ++k)
+    if ((uintptr_t)c.maps.p[k] & (lo_align - 1)) return false;
+  return true;
+}
+
+// the kernel argument structs' pointers: encode reads hi_in and writes lo_out, decode reads lo_in
+// and writes hi_out; the other pair stays null
+template <typename A, typename T, bool DEC>
+inline void bind(A& a, const CodecCall<T, DEC>& c) {
+  if constexpr (DEC) {
+    a.lo_in = c.in;
+    a.hi_out = c.out;
+  } else {
+    a.hi_in = c.in;
+    a.lo_out = c.out;
+  }
+  a.maps = c.maps;
+}
+
+// the 32-bit extents of the kernel argument structs (NSP = 2: no z members)
+template <int NSP, typename A>
+inline void set_extents(A& a, const Geo& g) {
+  if constexpr (NSP == 3) {
+    a.D = (int)g.n[0];
+    a.Lz = (int)g.L[0];
+    a.Ez = (int)g.E[0];
+    a.Lcz = (int)g.Lc[0];
+  }
+  a.H = (int)g.n[1]; a.W = (int)g.n[2];
+  a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
+  a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
+  a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+}
+
+// XCD-contiguous block order (xcd_block in kmp_wave.h) for batches that fill the 8 XCDs evenly:
+// ``per`` blocks per tile, 0 = identity order (KMP_W3_XCD / KMP_W2_XCD = 0, or B % 8 != 0)
+inline int xcd_per_tile(Opt xcd_opt, int64_t B, int64_t per) {
+  return (opt(xcd_opt, 1) && B % 8 == 0) ? (int)per : 0;
+}
 
 }  // namespace kmp

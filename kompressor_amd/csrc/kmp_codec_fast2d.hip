@@ -19,7 +19,7 @@
 //      x0.5 + truncation for these ranges), mod-2^k coder (utils.py:38-55), 8-byte stores.
 #include <cstdlib>
 
-#include "kmp_codec.h"
+#include "kmp_wave.h"
 
 namespace kmp {
 
@@ -41,90 +41,9 @@ struct F2 {
   int32_t lo_pitch, m_pitch, group_lds;  // u32 elements
 };
 
-__device__ __forceinline__ int lsrc(int r, int L, int E) {
-  int m = r % (2 * L);
-  if (m < 0) m += 2 * L;
-  m = m < L ? m : 2 * L - 1 - m;
-  int m2 = m % (2 * E);
-  return m2 < E ? m2 : 2 * E - 1 - m2;
-}
+using namespace wv;
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-template <int NT>
-__device__ __forceinline__ uint4 ld16(const void* p) {
-  if constexpr (NT) {
-    const u32x4 v = __builtin_nontemporal_load((const u32x4*)p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-  } else {
-    return *(const uint4*)p;
-  }
-}
-template <int NT>
-__device__ __forceinline__ uint2 ld8(const void* p) {
-  if constexpr (NT) {
-    const u32x2 v = __builtin_nontemporal_load((const u32x2*)p);
-    return make_uint2(v.x, v.y);
-  } else {
-    return *(const uint2*)p;
-  }
-}
-template <int NT>
-__device__ __forceinline__ void st16(void* p, uint4 v) {
-  if constexpr (NT) {
-    u32x4 w = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(w, (u32x4*)p);
-  } else {
-    *(uint4*)p = v;
-  }
-}
-template <int NT>
-__device__ __forceinline__ void st8(void* p, uint2 v) {
-  if constexpr (NT) {
-    u32x2 w = {v.x, v.y};
-    __builtin_nontemporal_store(w, (u32x2*)p);
-  } else {
-    *(uint2*)p = v;
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ uint32_t e16(const uint4& v, int e) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  if constexpr (sizeof(T) == 2) return (w[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
-  else return (w[e >> 2] >> ((e & 3) * 8)) & 0xffu;
-}
-template <typename T>
-__device__ __forceinline__ uint32_t e8(const uint2& v, int e) {
-  const uint32_t w[2] = {v.x, v.y};
-  if constexpr (sizeof(T) == 2) return (w[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
-  else return (w[e >> 2] >> ((e & 3) * 8)) & 0xffu;
-}
-template <typename T, int VX>
-__device__ __forceinline__ uint2 pack8(const uint32_t (&v)[VX]) {
-  if constexpr (sizeof(T) == 2) {
-    return make_uint2((v[0] & 0xffffu) | (v[1] << 16), (v[2] & 0xffffu) | (v[3] << 16));
-  } else {
-    return make_uint2((v[0] & 0xffu) | ((v[1] & 0xffu) << 8) | ((v[2] & 0xffu) << 16) | (v[3] << 24),
-                      (v[4] & 0xffu) | ((v[5] & 0xffu) << 8) | ((v[6] & 0xffu) << 16) | (v[7] << 24));
-  }
-}
-template <typename T, int VX>
-__device__ __forceinline__ uint4 pack16(const uint32_t (&ev)[VX], const uint32_t (&od)[VX]) {
-  if constexpr (sizeof(T) == 2) {
-    return make_uint4((ev[0] & 0xffffu) | (od[0] << 16), (ev[1] & 0xffffu) | (od[1] << 16),
-                      (ev[2] & 0xffffu) | (od[2] << 16), (ev[3] & 0xffffu) | (od[3] << 16));
-  } else {
-    uint32_t w[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      w[q] = (ev[2 * q] & 0xffu) | ((od[2 * q] & 0xffu) << 8) | ((ev[2 * q + 1] & 0xffu) << 16) | (od[2 * q + 1] << 24);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-  }
-}
-
-template <typename T, int P, bool DEC, int NT>
+template <typename T, int P, bool DEC>
 __global__ void __launch_bounds__(256) fast2d_kernel(F2 a) {
   constexpr int VX = 8 / (int)sizeof(T);
   constexpr int R = 2 * P + 2;
@@ -163,11 +82,11 @@ __global__ void __launch_bounds__(256) fast2d_kernel(F2 a) {
       return v;
     };
     for (int q = -P; q < 0; ++q) {
-      const int s = lsrc(q, a.Lx, a.Ex);
+      const int s = lsrc_mod(q, a.Lx, a.Ex);
       if (s >= X && s < X + VX) r[q - X] = pick(s);
     }
     for (int q = a.Ex; q <= a.Lx - 1 + P; ++q) {
-      const int s = lsrc(q, a.Lx, a.Ex);
+      const int s = lsrc_mod(q, a.Lx, a.Ex);
       if (s >= X && s < X + VX) r[q - X] = pick(s);
     }
   };
@@ -178,9 +97,9 @@ __global__ void __launch_bounds__(256) fast2d_kernel(F2 a) {
 
   auto load_lowres_row = [&](int j, uint4& hv, uint2& lv) {
     if (!live) return;
-    const int sy = lsrc(j, a.Ly, a.Ey);
-    if constexpr (DEC) lv = ld8<NT>(lin + (int64_t)sy * a.Ex + X);
-    else hv = ld16<NT>(hin + (int64_t)(2 * sy) * a.W + hx);
+    const int sy = lsrc_mod(j, a.Ly, a.Ey);
+    if constexpr (DEC) lv = ld8(lin + (int64_t)sy * a.Ex + X);
+    else hv = ld16(hin + (int64_t)(2 * sy) * a.W + hx);
   };
   uint4 pre_h = make_uint4(0, 0, 0, 0);
   uint2 pre_l = make_uint2(0, 0);
@@ -204,21 +123,21 @@ __global__ void __launch_bounds__(256) fast2d_kernel(F2 a) {
     if constexpr (!DEC) {
       if (do_out) {
         if constexpr (P == 0) e0 = keep_e;
-        else e0 = ld16<NT>(hin + (int64_t)(2 * c) * a.W + hx);
-        if (vy1) o0 = ld16<NT>(hin + (int64_t)(2 * c + 1) * a.W + hx);
+        else e0 = ld16(hin + (int64_t)(2 * c) * a.W + hx);
+        if (vy1) o0 = ld16(hin + (int64_t)(2 * c + 1) * a.W + hx);
       }
     } else {
       if (do_out) {
-        if (vy1) mv[0] = ld8<NT>((const T*)a.maps.p[0] + ((bb * a.Lcy + c) * a.Ex + X));
-        mv[1] = ld8<NT>((const T*)a.maps.p[1] + ((bb * a.Ey + c) * a.Ex + X));
-        if (vy1) mv[2] = ld8<NT>((const T*)a.maps.p[2] + ((bb * a.Lcy + c) * a.Ex + X));
+        if (vy1) mv[0] = ld8((const T*)a.maps.p[0] + ((bb * a.Lcy + c) * a.Ex + X));
+        mv[1] = ld8((const T*)a.maps.p[1] + ((bb * a.Ey + c) * a.Ex + X));
+        if (vy1) mv[2] = ld8((const T*)a.maps.p[2] + ((bb * a.Lcy + c) * a.Ex + X));
       }
     }
 
     {
       uint32_t nv[VX];
 #pragma unroll
-      for (int i = 0; i < VX; ++i) nv[i] = DEC ? e8<T>(cur_l, i) : e16<T>(cur_h, 2 * i);
+      for (int i = 0; i < VX; ++i) nv[i] = DEC ? el8<T>(cur_l, i) : el16<T>(cur_h, 2 * i);
       const int slot = ((j % R) + R) % R;
       if (live) write_nodes(lo_ring + slot * a.lo_pitch, nv);
     }
@@ -249,7 +168,7 @@ __global__ void __launch_bounds__(256) fast2d_kernel(F2 a) {
     if constexpr (DEC) {
       if constexpr (P == 0) {
 #pragma unroll
-        for (int i = 0; i < VX; ++i) own_lo[i] = e8<T>(keep_l, i);
+        for (int i = 0; i < VX; ++i) own_lo[i] = el8<T>(keep_l, i);
         keep_l = cur_l;
       } else {
         const uint32_t* row = lo_ring + (((c % R) + R) % R) * a.lo_pitch + kColOff + X;
@@ -293,24 +212,24 @@ __global__ void __launch_bounds__(256) fast2d_kernel(F2 a) {
       uint32_t lov[VX], res[3][VX];
 #pragma unroll
       for (int i = 0; i < VX; ++i) {
-        lov[i] = e16<T>(e0, 2 * i);
-        res[0][i] = (e16<T>(o0, 2 * i) - pred[0][i]) & MASK;      // LR (1,0)
-        res[1][i] = (e16<T>(e0, 2 * i + 1) - pred[1][i]) & MASK;  // UD (0,1)
-        res[2][i] = (e16<T>(o0, 2 * i + 1) - pred[2][i]) & MASK;  // C  (1,1)
+        lov[i] = el16<T>(e0, 2 * i);
+        res[0][i] = (el16<T>(o0, 2 * i) - pred[0][i]) & MASK;      // LR (1,0)
+        res[1][i] = (el16<T>(e0, 2 * i + 1) - pred[1][i]) & MASK;  // UD (0,1)
+        res[2][i] = (el16<T>(o0, 2 * i + 1) - pred[2][i]) & MASK;  // C  (1,1)
       }
-      st8<NT>((T*)a.lo_out + ((bb * a.Ey + c) * a.Ex + X), pack8<T, VX>(lov));
-      if (vy1) st8<NT>((T*)a.maps.p[0] + ((bb * a.Lcy + c) * a.Ex + X), pack8<T, VX>(res[0]));
-      st8<NT>((T*)a.maps.p[1] + ((bb * a.Ey + c) * a.Ex + X), pack8<T, VX>(res[1]));
-      if (vy1) st8<NT>((T*)a.maps.p[2] + ((bb * a.Lcy + c) * a.Ex + X), pack8<T, VX>(res[2]));
+      st8((T*)a.lo_out + ((bb * a.Ey + c) * a.Ex + X), pack8<T, VX>(lov));
+      if (vy1) st8((T*)a.maps.p[0] + ((bb * a.Lcy + c) * a.Ex + X), pack8<T, VX>(res[0]));
+      st8((T*)a.maps.p[1] + ((bb * a.Ey + c) * a.Ex + X), pack8<T, VX>(res[1]));
+      if (vy1) st8((T*)a.maps.p[2] + ((bb * a.Lcy + c) * a.Ex + X), pack8<T, VX>(res[2]));
     } else {
       uint32_t dv[3][VX];
 #pragma unroll
       for (int k = 0; k < 3; ++k)
 #pragma unroll
-        for (int i = 0; i < VX; ++i) dv[k][i] = (pred[k][i] + e8<T>(mv[k], i)) & MASK;
+        for (int i = 0; i < VX; ++i) dv[k][i] = (pred[k][i] + el8<T>(mv[k], i)) & MASK;
       T* h0 = hout + (int64_t)(2 * c) * a.W + hx;
-      st16<NT>(h0, pack16<T, VX>(own_lo, dv[1]));                // row 2c: lowres | UD
-      if (vy1) st16<NT>(h0 + a.W, pack16<T, VX>(dv[0], dv[2]));  // row 2c+1: LR | C
+      st16(h0, pack16<T, VX>(own_lo, dv[1]));                // row 2c: lowres | UD
+      if (vy1) st16(h0 + a.W, pack16<T, VX>(dv[0], dv[2]));  // row 2c+1: LR | C
     }
   }
 }
@@ -327,9 +246,7 @@ static bool geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pr
   const int64_t txn = g.E[2] / VX;
   if (txn * VX != g.E[2] || txn > 256 || txn < 1) return false;
   a.B = B;
-  a.H = (int)H; a.W = (int)W;
-  a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2]; a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  set_extents<2>(a, g);
   a.txn = (int)txn;
   a.groups = (int)(256 / txn);
   a.lo_pitch = (int)((kColOff + g.L[2] + P + VX + 3) / 4 * 4) + 4;
@@ -354,82 +271,25 @@ static bool geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pr
   return gblocks * nslab < ((int64_t)1 << 31);
 }
 
-template <typename T, bool DEC>
-static void launch(int P, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const F2& a) {
-  const bool nt = true;
-  switch (P * 2 + (nt ? 1 : 0)) {
-    case 0: fast2d_kernel<T, 0, DEC, 0><<<grid, block, lds, stream>>>(a); break;
-    case 1: fast2d_kernel<T, 0, DEC, 1><<<grid, block, lds, stream>>>(a); break;
-    case 2: fast2d_kernel<T, 1, DEC, 0><<<grid, block, lds, stream>>>(a); break;
-    case 3: fast2d_kernel<T, 1, DEC, 1><<<grid, block, lds, stream>>>(a); break;
-    case 4: fast2d_kernel<T, 2, DEC, 0><<<grid, block, lds, stream>>>(a); break;
-    default: fast2d_kernel<T, 2, DEC, 1><<<grid, block, lds, stream>>>(a); break;
-  }
-}
-
 }  // namespace f2
 
-template <typename T>
-int try_fast2d_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                      const MapPtrs& maps, const kmp_region* region, hipStream_t stream) {
-  {  // p == 0: the barrier-free wave kernel (kmp_codec_wave2d.hip)
-    int st = try_wave2d_encode<T>(hi, g, B, C, pred, lowres, maps, region, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_wave2dp_encode<T>(hi, g, B, C, pred, lowres, maps, region, stream);  // p = 1, 2
-    if (st != KMP_ERR_UNSUPPORTED) return st;
+// non-temporal highres / residual accesses (kmp_wave.h), as in kmp_codec_fast3d.hip
+template <typename T, bool DEC>
+int try_fast2d(const CodecCall<T, DEC>& c) {
+  f2::F2 a{};
+  dim3 grid, block;
+  size_t lds = 0;
+  if (!f2::geometry<T>(c.g, c.B, c.C, c.pred, c.region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 16, 8, 3)) return KMP_ERR_UNSUPPORTED;
+  bind(a, c);
+  switch (c.pred->padding) {
+    case 0: f2::fast2d_kernel<T, 0, DEC><<<grid, block, lds, c.stream>>>(a); break;
+    case 1: f2::fast2d_kernel<T, 1, DEC><<<grid, block, lds, c.stream>>>(a); break;
+    default: f2::fast2d_kernel<T, 2, DEC><<<grid, block, lds, c.stream>>>(a); break;
   }
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    f2::F2 a{};
-    dim3 grid, block;
-    size_t lds = 0;
-    if (!f2::geometry<T>(g, B, C, pred, region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 3; ++k)
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    f2::launch<T, false>(pred->padding, grid, block, lds, stream, a);
-    return check_launch("fast2d_encode");
-  }
-  return KMP_ERR_UNSUPPORTED;
+  return check_launch(DEC ? "fast2d_decode" : "fast2d_encode");
 }
 
-template <typename T>
-int try_fast2d_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                      const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream) {
-  {
-    int st = try_wave2d_decode<T>(lowres, maps, g, B, C, pred, hi, region, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_wave2dp_decode<T>(lowres, maps, g, B, C, pred, hi, region, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-  }
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    f2::F2 a{};
-    dim3 grid, block;
-    size_t lds = 0;
-    if (!f2::geometry<T>(g, B, C, pred, region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 3; ++k) {
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    f2::launch<T, true>(pred->padding, grid, block, lds, stream, a);
-    return check_launch("fast2d_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_INST2(T)                                                                                             \
-  template int try_fast2d_encode<T>(const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,          \
-                                    const MapPtrs&, const kmp_region*, hipStream_t);                           \
-  template int try_fast2d_decode<T>(const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,                   \
-                                    const kmp_predictor*, T*, const kmp_region*, hipStream_t);
-KMP_INST2(uint8_t)
-KMP_INST2(uint16_t)
-KMP_INST2(int32_t)
-KMP_INST2(uint32_t)
+KMP_INST_FAMILY_U8_U16(try_fast2d)
 
 }  // namespace kmp

@@ -2,7 +2,7 @@
 //
 // Eligible: C == 1, uint8/uint16, mean predictor with p <= 2, W even with W*sizeof(T) % 16 == 0,
 // (W/2 / VX) * ceil(H/2) <= 1024 threads, 16-B aligned highres, 8-B aligned lowres/maps, and a
-// region (if any) that only restricts z.  Everything else goes to kmp_codec_generic.hip.
+// region (if any) that only restricts z.
 //
 // Output-frame view: output block o = (Z, Y, X) in [0, E)^3 owns the
 // 2x2x2 highres block at 2o; the lowres and the 7 maps are its 8 parity classes, each stored
@@ -23,7 +23,7 @@
 // once) plus one lowres halo plane per slab.
 #include <cstdlib>
 
-#include "kmp_codec.h"
+#include "kmp_wave.h"
 
 namespace kmp {
 
@@ -44,94 +44,17 @@ struct F3 {
   int32_t lo_pitch, lo_plane, m_pitch, m_plane;
 };
 
-__device__ __forceinline__ int lsrc(int r, int L, int E) {
-  // lowres source index of padded node r: neighbourhood symmetric pad, then even reflect pad
-  int m = r % (2 * L);
-  if (m < 0) m += 2 * L;
-  m = m < L ? m : 2 * L - 1 - m;
-  int m2 = m % (2 * E);
-  m2 = m2 < E ? m2 : 2 * E - 1 - m2;
-  return m2;
-}
+using wv::el16;
+using wv::el8;
+using wv::ld16;
+using wv::ld8;
+using wv::lsrc_mod;
+using wv::pack16;
+using wv::pack8;
+using wv::st16;
+using wv::st8;
 
-template <typename T>
-__device__ __forceinline__ uint32_t elem_v16(const uint4& v, int e) {  // element e of a 16-byte vector
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  if constexpr (sizeof(T) == 2) return (w[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
-  else return (w[e >> 2] >> ((e & 3) * 8)) & 0xffu;
-}
-template <typename T>
-__device__ __forceinline__ uint32_t elem_v8(const uint2& v, int e) {  // element e of an 8-byte vector
-  const uint32_t w[2] = {v.x, v.y};
-  if constexpr (sizeof(T) == 2) return (w[e >> 1] >> ((e & 1) * 16)) & 0xffffu;
-  else return (w[e >> 2] >> ((e & 3) * 8)) & 0xffu;
-}
-template <typename T, int VX>
-__device__ __forceinline__ uint2 pack_v8(const uint32_t (&v)[VX]) {
-  if constexpr (sizeof(T) == 2) {
-    return make_uint2((v[0] & 0xffffu) | (v[1] << 16), (v[2] & 0xffffu) | (v[3] << 16));
-  } else {
-    return make_uint2((v[0] & 0xffu) | ((v[1] & 0xffu) << 8) | ((v[2] & 0xffu) << 16) | (v[3] << 24),
-                      (v[4] & 0xffu) | ((v[5] & 0xffu) << 8) | ((v[6] & 0xffu) << 16) | (v[7] << 24));
-  }
-}
-template <typename T, int VX>
-__device__ __forceinline__ uint4 pack_v16(const uint32_t (&ev)[VX], const uint32_t (&od)[VX]) {
-  if constexpr (sizeof(T) == 2) {
-    return make_uint4((ev[0] & 0xffffu) | (od[0] << 16), (ev[1] & 0xffffu) | (od[1] << 16),
-                      (ev[2] & 0xffffu) | (od[2] << 16), (ev[3] & 0xffffu) | (od[3] << 16));
-  } else {
-    uint32_t w[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      w[q] = (ev[2 * q] & 0xffu) | ((od[2 * q] & 0xffu) << 8) | ((ev[2 * q + 1] & 0xffu) << 16) | (od[2 * q + 1] << 24);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-  }
-}
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-// Streaming global access.  NT = 1 marks every highres / residual byte as non-temporal (each is
-// touched exactly once per pass), NT = 0 uses the default cache policy.
-template <int NT>
-__device__ __forceinline__ uint4 ld16(const void* p) {
-  if constexpr (NT) {
-    const u32x4 v = __builtin_nontemporal_load((const u32x4*)p);
-    return make_uint4(v.x, v.y, v.z, v.w);
-  } else {
-    return *(const uint4*)p;
-  }
-}
-template <int NT>
-__device__ __forceinline__ uint2 ld8(const void* p) {
-  if constexpr (NT) {
-    const u32x2 v = __builtin_nontemporal_load((const u32x2*)p);
-    return make_uint2(v.x, v.y);
-  } else {
-    return *(const uint2*)p;
-  }
-}
-template <int NT>
-__device__ __forceinline__ void st16(void* p, uint4 v) {
-  if constexpr (NT) {
-    u32x4 w = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(w, (u32x4*)p);
-  } else {
-    *(uint4*)p = v;
-  }
-}
-template <int NT>
-__device__ __forceinline__ void st8(void* p, uint2 v) {
-  if constexpr (NT) {
-    u32x2 w = {v.x, v.y};
-    __builtin_nontemporal_store(w, (u32x2*)p);
-  } else {
-    *(uint2*)p = v;
-  }
-}
-
-template <typename T, int P, bool DEC, int NT>
+template <typename T, int P, bool DEC>
 __global__ void __launch_bounds__(1024) fast3d_kernel(F3 a) {
   constexpr int VX = 8 / (int)sizeof(T);  // outputs per thread along x (16 B of highres row)
   constexpr int R = 2 * P + 2;            // lowres planes in flight
@@ -179,19 +102,19 @@ __global__ void __launch_bounds__(1024) fast3d_kernel(F3 a) {
         return v;
       };
       for (int q = -P; q < 0; ++q) {
-        const int s = lsrc(q, a.Lx, a.Ex);
+        const int s = lsrc_mod(q, a.Lx, a.Ex);
         if (s >= X && s < X + VX) row[q - X] = pick(s);
       }
       for (int q = a.Ex; q <= a.Lx - 1 + P; ++q) {
-        const int s = lsrc(q, a.Lx, a.Ex);
+        const int s = lsrc_mod(q, a.Lx, a.Ex);
         if (s >= X && s < X + VX) row[q - X] = pick(s);
       }
     };
     put_row(Y);
     for (int r = -P; r < 0; ++r)
-      if (lsrc(r, a.Ly, a.Ey) == Y) put_row(r);
+      if (lsrc_mod(r, a.Ly, a.Ey) == Y) put_row(r);
     for (int r = a.Ey; r <= a.Ly - 1 + P; ++r)
-      if (lsrc(r, a.Ly, a.Ey) == Y) put_row(r);
+      if (lsrc_mod(r, a.Ly, a.Ey) == Y) put_row(r);
   };
 
   const int jstart = (Z0 - 1 > 0 ? Z0 - 1 : 0) - P;
@@ -200,9 +123,9 @@ __global__ void __launch_bounds__(1024) fast3d_kernel(F3 a) {
 
   // Prefetched lowres source row for the current step.
   auto load_lowres_row = [&](int j, uint4& hv, uint2& lv) {
-    const int sz = lsrc(j, a.Lz, a.Ez);
-    if constexpr (DEC) lv = ld8<NT>(lin + (int64_t)sz * lplane + (int64_t)Y * a.Ex + X);
-    else hv = ld16<NT>(hin + (int64_t)(2 * sz) * hplane + (int64_t)(2 * Y) * hrow + hx);
+    const int sz = lsrc_mod(j, a.Lz, a.Ez);
+    if constexpr (DEC) lv = ld8(lin + (int64_t)sz * lplane + (int64_t)Y * a.Ex + X);
+    else hv = ld16(hin + (int64_t)(2 * sz) * hplane + (int64_t)(2 * Y) * hrow + hx);
   };
   uint4 pre_h = make_uint4(0, 0, 0, 0);
   uint2 pre_l = make_uint2(0, 0);
@@ -230,20 +153,20 @@ __global__ void __launch_bounds__(1024) fast3d_kernel(F3 a) {
     uint4 nxt1 = make_uint4(0, 0, 0, 0);
     if constexpr (!DEC) {
       if constexpr (P == 0) {
-        if (j >= Z0 && j < Z1 && vy1) nxt1 = ld16<NT>(hin + (int64_t)(2 * j) * hplane + (int64_t)(2 * Y + 1) * hrow + hx);
+        if (j >= Z0 && j < Z1 && vy1) nxt1 = ld16(hin + (int64_t)(2 * j) * hplane + (int64_t)(2 * Y + 1) * hrow + hx);
         if (do_out) {
           e0 = keep0;
           e1 = keep1;
         }
       } else {
         if (do_out) {
-          e0 = ld16<NT>(hin + (int64_t)(2 * c) * hplane + (int64_t)(2 * Y) * hrow + hx);
-          if (vy1) e1 = ld16<NT>(hin + (int64_t)(2 * c) * hplane + (int64_t)(2 * Y + 1) * hrow + hx);
+          e0 = ld16(hin + (int64_t)(2 * c) * hplane + (int64_t)(2 * Y) * hrow + hx);
+          if (vy1) e1 = ld16(hin + (int64_t)(2 * c) * hplane + (int64_t)(2 * Y + 1) * hrow + hx);
         }
       }
       if (do_out && vz1) {
-        o0 = ld16<NT>(hin + (int64_t)(2 * c + 1) * hplane + (int64_t)(2 * Y) * hrow + hx);
-        if (vy1) o1 = ld16<NT>(hin + (int64_t)(2 * c + 1) * hplane + (int64_t)(2 * Y + 1) * hrow + hx);
+        o0 = ld16(hin + (int64_t)(2 * c + 1) * hplane + (int64_t)(2 * Y) * hrow + hx);
+        if (vy1) o1 = ld16(hin + (int64_t)(2 * c + 1) * hplane + (int64_t)(2 * Y + 1) * hrow + hx);
       }
     } else {
       if (do_out) {
@@ -254,7 +177,7 @@ __global__ void __launch_bounds__(1024) fast3d_kernel(F3 a) {
           if ((par[0] && !vz1) || (par[1] && !vy1)) continue;
           const int64_t ez = par[0] ? a.Lcz : a.Ez, ey = par[1] ? a.Lcy : a.Ey;
           const T* mp = (const T*)a.maps.p[k] + ((b * ez + c) * ey + Y) * a.Ex + X;
-          mv[k] = ld8<NT>(mp);
+          mv[k] = ld8(mp);
         }
       }
     }
@@ -263,7 +186,7 @@ __global__ void __launch_bounds__(1024) fast3d_kernel(F3 a) {
     {
       uint32_t nv[VX];
 #pragma unroll
-      for (int i = 0; i < VX; ++i) nv[i] = DEC ? elem_v8<T>(cur_l, i) : elem_v16<T>(cur_h, 2 * i);
+      for (int i = 0; i < VX; ++i) nv[i] = DEC ? el8<T>(cur_l, i) : el16<T>(cur_h, 2 * i);
       const int slot = ((j % R) + R) % R;
       write_nodes(lo_ring + slot * a.lo_plane, nv);
     }
@@ -309,7 +232,7 @@ __global__ void __launch_bounds__(1024) fast3d_kernel(F3 a) {
     if constexpr (DEC) {
       if constexpr (P == 0) {
 #pragma unroll
-        for (int i = 0; i < VX; ++i) own_lo[i] = elem_v8<T>(keep_l, i);
+        for (int i = 0; i < VX; ++i) own_lo[i] = el8<T>(keep_l, i);
         keep_l = cur_l;
       } else {
         const int slot = (((c % R) + R) % R);
@@ -372,17 +295,17 @@ __global__ void __launch_bounds__(1024) fast3d_kernel(F3 a) {
       uint32_t res[7][VX], lov[VX];
 #pragma unroll
       for (int i = 0; i < VX; ++i) {
-        lov[i] = elem_v16<T>(e0, 2 * i);
-        res[0][i] = (elem_v16<T>(o1, 2 * i) - pred[0][i]) & MASK;      // LR (1,1,0)
-        res[1][i] = (elem_v16<T>(o0, 2 * i + 1) - pred[1][i]) & MASK;  // UD (1,0,1)
-        res[2][i] = (elem_v16<T>(e1, 2 * i + 1) - pred[2][i]) & MASK;  // FB (0,1,1)
-        res[3][i] = (elem_v16<T>(o1, 2 * i + 1) - pred[3][i]) & MASK;  // C  (1,1,1)
-        res[4][i] = (elem_v16<T>(o0, 2 * i) - pred[4][i]) & MASK;      // Z  (1,0,0)
-        res[5][i] = (elem_v16<T>(e1, 2 * i) - pred[5][i]) & MASK;      // Y  (0,1,0)
-        res[6][i] = (elem_v16<T>(e0, 2 * i + 1) - pred[6][i]) & MASK;  // X  (0,0,1)
+        lov[i] = el16<T>(e0, 2 * i);
+        res[0][i] = (el16<T>(o1, 2 * i) - pred[0][i]) & MASK;      // LR (1,1,0)
+        res[1][i] = (el16<T>(o0, 2 * i + 1) - pred[1][i]) & MASK;  // UD (1,0,1)
+        res[2][i] = (el16<T>(e1, 2 * i + 1) - pred[2][i]) & MASK;  // FB (0,1,1)
+        res[3][i] = (el16<T>(o1, 2 * i + 1) - pred[3][i]) & MASK;  // C  (1,1,1)
+        res[4][i] = (el16<T>(o0, 2 * i) - pred[4][i]) & MASK;      // Z  (1,0,0)
+        res[5][i] = (el16<T>(e1, 2 * i) - pred[5][i]) & MASK;      // Y  (0,1,0)
+        res[6][i] = (el16<T>(e0, 2 * i + 1) - pred[6][i]) & MASK;  // X  (0,0,1)
       }
       T* lo = (T*)a.lo_out + ((b * a.Ez + c) * a.Ey + Y) * a.Ex + X;
-      st8<NT>(lo, pack_v8<T, VX>(lov));
+      st8(lo, pack8<T, VX>(lov));
 #pragma unroll
       for (int k = 0; k < 7; ++k) {
         int par[3];
@@ -390,21 +313,21 @@ __global__ void __launch_bounds__(1024) fast3d_kernel(F3 a) {
         if ((par[0] && !vz1) || (par[1] && !vy1)) continue;
         const int64_t ez = par[0] ? a.Lcz : a.Ez, ey = par[1] ? a.Lcy : a.Ey;
         T* mp = (T*)a.maps.p[k] + ((b * ez + c) * ey + Y) * a.Ex + X;
-        st8<NT>(mp, pack_v8<T, VX>(res[k]));
+        st8(mp, pack8<T, VX>(res[k]));
       }
     } else {
       uint32_t dv[7][VX];
 #pragma unroll
       for (int k = 0; k < 7; ++k)
 #pragma unroll
-        for (int i = 0; i < VX; ++i) dv[k][i] = (pred[k][i] + elem_v8<T>(mv[k], i)) & MASK;
+        for (int i = 0; i < VX; ++i) dv[k][i] = (pred[k][i] + el8<T>(mv[k], i)) & MASK;
       T* h0 = hout + (int64_t)(2 * c) * hplane + (int64_t)(2 * Y) * hrow + hx;
-      st16<NT>(h0, pack_v16<T, VX>(own_lo, dv[6]));                  // plane 2c, row 2Y: lowres | X
-      if (vy1) st16<NT>(h0 + hrow, pack_v16<T, VX>(dv[5], dv[2]));  // plane 2c, row 2Y+1: Y | FB
+      st16(h0, pack16<T, VX>(own_lo, dv[6]));                  // plane 2c, row 2Y: lowres | X
+      if (vy1) st16(h0 + hrow, pack16<T, VX>(dv[5], dv[2]));  // plane 2c, row 2Y+1: Y | FB
       if (vz1) {
         T* h1 = h0 + hplane;
-        st16<NT>(h1, pack_v16<T, VX>(dv[4], dv[1]));                  // plane 2c+1, row 2Y: Z | UD
-        if (vy1) st16<NT>(h1 + hrow, pack_v16<T, VX>(dv[0], dv[3]));  // plane 2c+1, row 2Y+1: LR | C
+        st16(h1, pack16<T, VX>(dv[4], dv[1]));                  // plane 2c+1, row 2Y: Z | UD
+        if (vy1) st16(h1 + hrow, pack16<T, VX>(dv[0], dv[3]));  // plane 2c+1, row 2Y+1: LR | C
       }
     }
   }
@@ -417,7 +340,6 @@ template <typename T>
 static bool fast3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, const kmp_region* region,
                             F3& a, dim3& grid, dim3& block, size_t& lds) {
   constexpr int VX = 8 / (int)sizeof(T);
-  if (!(std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value)) return false;
   if (opt(OPT_DISABLE_FAST, 0)) return false;
   if (C != 1 || pred->kind != KMP_PRED_MEAN || pred->padding > 2) return false;
   const int P = pred->padding;
@@ -427,17 +349,9 @@ static bool fast3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predic
   if (txn * VX != g.E[2]) return false;
   const int64_t threads = txn * g.E[1];
   if (threads > 1024 || threads < 1) return false;
-  int64_t zb = 0, ze = g.E[0];
-  if (region) {
-    if (region->begin[1] > 0 || region->begin[2] > 0 || region->end[1] < g.E[1] || region->end[2] < g.E[2]) return false;
-    zb = region->begin[0] < 0 ? 0 : region->begin[0];
-    ze = region->end[0] > g.E[0] ? g.E[0] : region->end[0];
-    if (ze <= zb) return false;
-  }
-  a.D = (int)g.n[0]; a.H = (int)g.n[1]; a.W = (int)g.n[2];
-  a.Lz = (int)g.L[0]; a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
-  a.Ez = (int)g.E[0]; a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcz = (int)g.Lc[0]; a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  int64_t zb, ze;
+  if (!region_span(region, g, 0, zb, ze)) return false;
+  set_extents<3>(a, g);
   a.txn = (int)txn;
   // LDS: lowres planes rows [-P, Ly-1+P], cols [-P, Lx-1+P] at kColOff; cell planes rows [-1, Lcy), cols [-1, Lcx)
   a.lo_pitch = (int)((kColOff + g.L[2] + P + VX + 3) / 4 * 4) + 1 * 4;
@@ -464,103 +378,24 @@ static bool fast3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predic
   return B * nslab < (int64_t)1 << 31;
 }
 
+// every highres / residual byte is touched once per pass and moves non-temporally (kmp_wave.h's
+// ld16 / st8 ...; measured 1-2 % faster than the default policy, profiles/round1/sweep_volume_p0.log)
 template <typename T, bool DEC>
-static void launch_fast3d(int P, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const F3& a) {
-  const bool nt = true;  // measured: NT 1-2 % faster (profiles/round1/sweep_volume_p0.log)
-  switch (P * 2 + (nt ? 1 : 0)) {
-    case 0: fast3d_kernel<T, 0, DEC, 0><<<grid, block, lds, stream>>>(a); break;
-    case 1: fast3d_kernel<T, 0, DEC, 1><<<grid, block, lds, stream>>>(a); break;
-    case 2: fast3d_kernel<T, 1, DEC, 0><<<grid, block, lds, stream>>>(a); break;
-    case 3: fast3d_kernel<T, 1, DEC, 1><<<grid, block, lds, stream>>>(a); break;
-    case 4: fast3d_kernel<T, 2, DEC, 0><<<grid, block, lds, stream>>>(a); break;
-    default: fast3d_kernel<T, 2, DEC, 1><<<grid, block, lds, stream>>>(a); break;
+int try_fast3d(const CodecCall<T, DEC>& c) {
+  F3 a{};
+  dim3 grid, block;
+  size_t lds = 0;
+  if (!fast3d_geometry<T>(c.g, c.B, c.C, c.pred, c.region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 16, 8, 7)) return KMP_ERR_UNSUPPORTED;
+  bind(a, c);
+  switch (c.pred->padding) {
+    case 0: fast3d_kernel<T, 0, DEC><<<grid, block, lds, c.stream>>>(a); break;
+    case 1: fast3d_kernel<T, 1, DEC><<<grid, block, lds, c.stream>>>(a); break;
+    default: fast3d_kernel<T, 2, DEC><<<grid, block, lds, c.stream>>>(a); break;
   }
+  return check_launch(DEC ? "fast3d_decode" : "fast3d_encode");
 }
 
-template <typename T>
-int try_fast_encode(int nsp, const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                    const MapPtrs& maps, const kmp_region* region, void* ws, size_t ws_bytes, hipStream_t stream) {
-  if (nsp != 3) return try_fast2d_encode<T>(hi, g, B, C, pred, lowres, maps, region, stream);
-  {  // p == 0: the barrier-free wave kernel (kmp_codec_wave3d.hip) / fused linear (kmp_codec_linear3d.hip)
-    int st = try_wave3d_encode<T>(hi, g, B, C, pred, lowres, maps, region, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_wave3d32_encode<T>(hi, g, B, C, pred, lowres, maps, region, stream);  // 32-bit samples
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_linear3m_encode<T>(hi, g, B, C, pred, lowres, maps, region, stream);  // matrix-core linear p = 0
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_linear3d_encode<T>(hi, g, B, C, pred, lowres, maps, region, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_wave3dp_encode<T>(hi, g, B, C, pred, lowres, maps, region, stream);  // p = 1, 2
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_linear3dp_encode<T>(hi, g, B, C, pred, lowres, maps, region, ws, ws_bytes, stream);  // linear p = 1
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_linear3pm_encode<T>(hi, g, B, C, pred, lowres, maps, region, ws, ws_bytes, stream);  // matrix-core linear p = 1
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-  }
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    F3 a{};
-    dim3 grid, block;
-    size_t lds = 0;
-    if (!fast3d_geometry<T>(g, B, C, pred, region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k)
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    launch_fast3d<T, false>(pred->padding, grid, block, lds, stream, a);
-    return check_launch("fast3d_encode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-template <typename T>
-int try_fast_decode(int nsp, const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                    const kmp_predictor* pred, T* hi, const kmp_region* region, void* ws, size_t ws_bytes,
-                    hipStream_t stream) {
-  if (nsp != 3) return try_fast2d_decode<T>(lowres, maps, g, B, C, pred, hi, region, stream);
-  {
-    int st = try_wave3d_decode<T>(lowres, maps, g, B, C, pred, hi, region, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_wave3d32_decode<T>(lowres, maps, g, B, C, pred, hi, region, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_linear3m_decode<T>(lowres, maps, g, B, C, pred, hi, region, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_linear3d_decode<T>(lowres, maps, g, B, C, pred, hi, region, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_wave3dp_decode<T>(lowres, maps, g, B, C, pred, hi, region, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_linear3dp_decode<T>(lowres, maps, g, B, C, pred, hi, region, ws, ws_bytes, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-    st = try_linear3pm_decode<T>(lowres, maps, g, B, C, pred, hi, region, ws, ws_bytes, stream);
-    if (st != KMP_ERR_UNSUPPORTED) return st;
-  }
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    F3 a{};
-    dim3 grid, block;
-    size_t lds = 0;
-    if (!fast3d_geometry<T>(g, B, C, pred, region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k) {
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    launch_fast3d<T, true>(pred->padding, grid, block, lds, stream, a);
-    return check_launch("fast3d_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_INST(T)                                                                                              \
-  template int try_fast_encode<T>(int, const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,         \
-                                  const MapPtrs&, const kmp_region*, void*, size_t, hipStream_t);                \
-  template int try_fast_decode<T>(int, const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,                  \
-                                  const kmp_predictor*, T*, const kmp_region*, void*, size_t, hipStream_t);
-KMP_INST(uint8_t)
-KMP_INST(uint16_t)
-KMP_INST(int32_t)
-KMP_INST(uint32_t)
+KMP_INST_FAMILY_U8_U16(try_fast3d)
 
 }  // namespace kmp

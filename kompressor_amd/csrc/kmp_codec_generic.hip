@@ -696,10 +696,7 @@ static Frame make_frame(int nsp, const Geo& g, const kmp_region* region) {
   Frame f{};
   for (int a = 0; a < 3; ++a) {
     int64_t lo = 0, hi = g.E[a];
-    if (region && a >= 3 - nsp) {
-      lo = region->begin[a] < 0 ? 0 : region->begin[a];
-      hi = region->end[a] > g.E[a] ? g.E[a] : region->end[a];
-    }
+    if (region && a >= 3 - nsp) region_clamp(region, g, a, lo, hi);
     f.begin[a] = lo;
     f.ext[a] = hi > lo ? hi - lo : 0;
   }
@@ -929,6 +926,47 @@ static int dispatch_natural(int dtype, int coder, F&& f) {
                                        std::to_string(dtype) + " coder " + std::to_string(coder));
 }
 
+// ------------------------------------------------------------------------------------------
+// Kernel selection: THE dispatch table.  The one-pass families (kmp_codec.h) of a request's
+// (spatial rank, sample width), in the order they are tried; encode and decode walk the same list,
+// so one family serves both directions of a configuration.  The first family that does not answer
+// KMP_ERR_UNSUPPORTED served (or failed) the call; when none takes it, the generic two-pass path
+// of this file does.  A family earlier in a list shadows the later ones wherever both are eligible:
+// the barrier-free wave kernels before the fused linear kernels (disjoint predictor kinds), the
+// LDS kernels (fast3d / fast2d) last as the fallback for the geometries the wave kernels refuse.
+// ------------------------------------------------------------------------------------------
+template <typename T, bool DEC>
+static int try_one_pass(const CodecCall<T, DEC>& c) {
+  using Try = int (*)(const CodecCall<T, DEC>&);
+  const Try* family;  // nullptr-terminated
+  if constexpr (sizeof(T) == 4) {
+    static constexpr Try volume[] = {try_wave3d32<T, DEC>, nullptr};
+    static constexpr Try image[] = {nullptr};
+    family = c.nsp == 3 ? volume : image;
+  } else {
+    static constexpr Try volume[] = {
+        try_wave3d<T, DEC>,     // mean p = 0
+        try_linear3m<T, DEC>,   // matrix-core linear p = 0
+        try_linear3d<T, DEC>,   // f32 linear p = 0
+        try_wave3dp<T, DEC>,    // mean p = 1, 2
+        try_linear3dp<T, DEC>,  // f32 linear p = 1
+        try_linear3pm<T, DEC>,  // matrix-core linear p = 1
+        try_fast3d<T, DEC>,     // mean p <= 2, the LDS kernel
+        nullptr};
+    static constexpr Try image[] = {
+        try_wave2d<T, DEC>,   // mean / f32 linear p = 0
+        try_wave2dp<T, DEC>,  // mean p = 1, 2
+        try_fast2d<T, DEC>,   // mean p <= 2, the LDS kernel
+        nullptr};
+    family = c.nsp == 3 ? volume : image;
+  }
+  for (; *family; ++family) {
+    const int st = (*family)(c);
+    if (st != KMP_ERR_UNSUPPORTED) return st;
+  }
+  return KMP_ERR_UNSUPPORTED;
+}
+
 static int check_predictor(const kmp_predictor* pred, int dtype) {
   KMP_REQUIRE(pred, "null predictor");
   KMP_REQUIRE(pred->padding >= 0, "negative padding");
@@ -959,11 +997,11 @@ int codec_encode(int nsp, int dtype, const void* highres, int64_t B, const int64
   return dispatch_natural(dtype, coder, [&](auto tag, auto coder_c) {
     using T = decltype(tag);
     constexpr int CODER = decltype(coder_c)::value;
-    int st = try_fast_encode<T>(nsp, (const T*)highres, g, B, C, pred, (T*)lowres_out, maps, region, ws, ws_bytes,
-                                stream);
+    const CodecCall<T, false> c{nsp, g, B, C, pred, region, (const T*)highres, (T*)lowres_out,
+                                maps, ws, ws_bytes, stream};
+    const int st = try_one_pass(c);
     if (st != KMP_ERR_UNSUPPORTED) return st;
-    return encode_generic_t<T, CODER>((const T*)highres, g, nsp, B, C, pred, (T*)lowres_out, maps, region, ws,
-                                      ws_bytes, stream);
+    return encode_generic_t<T, CODER>(c.in, g, nsp, B, C, pred, c.out, maps, region, ws, ws_bytes, stream);
   });
 }
 
@@ -987,11 +1025,13 @@ int codec_decode(int nsp, int dtype, const void* lowres, const void* const* maps
   return dispatch_natural(dtype, coder, [&](auto tag, auto coder_c) {
     using T = decltype(tag);
     constexpr int CODER = decltype(coder_c)::value;
-    int st = try_fast_decode<T>(nsp, (const T*)lowres, maps, g, B, C, pred, (T*)highres_out, region, ws, ws_bytes,
-                                stream);
+    MapPtrs mp{};  // the kernel argument structs hold one pointer type; a decode only reads through it
+    for (int k = 0; k < kMaxMaps; ++k) mp.p[k] = const_cast<void*>(maps.p[k]);
+    const CodecCall<T, true> c{nsp, g, B, C, pred, region, (const T*)lowres, (T*)highres_out,
+                               mp, ws, ws_bytes, stream};
+    const int st = try_one_pass(c);
     if (st != KMP_ERR_UNSUPPORTED) return st;
-    return decode_generic_t<T, CODER>((const T*)lowres, maps, g, nsp, B, C, pred, (T*)highres_out, region, ws,
-                                      ws_bytes, stream);
+    return decode_generic_t<T, CODER>(c.in, maps, g, nsp, B, C, pred, c.out, region, ws, ws_bytes, stream);
   });
 }
 

@@ -36,9 +36,9 @@ struct L3 {
   const void* lo_in;
   void* lo_out;
   MapPtrs maps;
-  const float* W;  // [8, 19] row-major
-  const float* b;  // [19]
-  int32_t D, H, W_;
+  const float* wt;  // [8, 19] row-major
+  const float* b;   // [19]
+  int32_t D, H, W;
   int32_t Lz, Ly, Lx, Ez, Ey, Ex, Lcz, Lcy, Lcx;
   int32_t zbegin, zend;
   int32_t txn, rows, nwv;
@@ -46,14 +46,6 @@ struct L3 {
   int32_t uld;
   int32_t full;  // Lcy == Ey and Lcx == Ex: the FULL kernel serves the call
 };
-
-// astype(T) for u8/u16: trunc, saturate, NaN -> 0.  v_cvt_u32_f32 truncates and saturates to
-// [0, 2^32-1] with NaN -> 0, so one integer min finishes it (cvt_sat, kmp_wave.h): 2 VALU per value,
-// where fminf(fmaxf()) compiled to med3 + cvt plus a canonicalising v_max on some of them
-template <typename T>
-__device__ __forceinline__ uint32_t cast_t(float v) {
-  return cvt_sat<T>(v);
-}
 
 // Node values are kept as f32 pairs laid out for the packed FMAs: for the 4 cells X+4g .. X+4g+3
 // of a group, NP[.][g][0] = {node 4g, 4g+2}, [1] = {4g+1, 4g+3}, [2] = {4g+2, 4g+4}.  Cells
@@ -95,10 +87,10 @@ __device__ __forceinline__ void channel(const f32x2 (&NP)[3][G][3], const f32x2 
     a02 = __builtin_elementwise_fma(R[dx], wv2, a02);
     a13 = __builtin_elementwise_fma(R[1 + dx], wv2, a13);
   }
-  out[0] = cast_t<T>(a02.x);
-  out[1] = cast_t<T>(a13.x);
-  out[2] = cast_t<T>(a02.y);
-  out[3] = cast_t<T>(a13.y);
+  out[0] = cvt_sat<T>(a02.x);
+  out[1] = cvt_sat<T>(a13.x);
+  out[2] = cvt_sat<T>(a02.y);
+  out[3] = cvt_sat<T>(a13.y);
 }
 
 constexpr int kXch = 5;  // channels exchanged downwards: 3, 9, 10, 16 (plane c), 17 (plane c-1)
@@ -125,18 +117,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   // LDS: the exchange rows [wave][kXch][Ex]
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   uint32_t* xrow = smem;
-  const CFloat Wc = (CFloat)a.W, Bc = (CFloat)a.b;
+  const CFloat Wc = (CFloat)a.wt, Bc = (CFloat)a.b;
 
   const int lane = threadIdx.x & 63;
   const int wv_ = threadIdx.x >> 6;
   const int tx = lane & (a.txn - 1);
   const int r = lane >> __builtin_ctz(a.txn);
   const int X = tx * VX;
-  int blk = (int)blockIdx.x;
-  if (a.xcd_per > 0) {
-    const int x = blk % 8, k = blk / 8;
-    blk = ((k / a.xcd_per) * 8 + x) * a.xcd_per + (k % a.xcd_per);
-  }
+  int blk = xcd_block((int)blockIdx.x, a.xcd_per);
   const int nplanes = a.zend - a.zbegin;
   const int c = a.zbegin + blk % nplanes;
   const int64_t b = blk / nplanes;
@@ -159,13 +147,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   const CFloat WcP = (FULL && !vz1) ? Zc : Wc, BcP = (FULL && !vz1) ? Zc + 152 : Bc;
   const CFloat WcQ = (FULL && !vz0) ? Zc : Wc, BcQ = (FULL && !vz0) ? Zc + 152 : Bc;
 
-  const int hplane = a.H * a.W_;
+  const int hplane = a.H * a.W;
   const int lplane = a.Ey * a.Ex;
   const T* hin = DEC ? nullptr : (const T*)a.hi_in + b * (int64_t)a.D * hplane;
   T* hout = DEC ? (T*)a.hi_out + b * (int64_t)a.D * hplane : nullptr;
   const T* lin = DEC ? (const T*)a.lo_in + b * (int64_t)a.Ez * lplane : nullptr;
   const int hx = 2 * X;
-  const int ho_own = 2 * Yc * a.W_ + hx, ho_dn = 2 * ydn * a.W_ + hx;
+  const int ho_own = 2 * Yc * a.W + hx, ho_dn = 2 * ydn * a.W + hx;
   const int lo_own = Yc * a.Ex + X, lo_dn = ydn * a.Ex + X;
 
   const T* mbase[7];
@@ -237,7 +225,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
       own[t] = ld16c(p + ho_own);
       dn[t] = ld16c(p + ho_dn);
     }
-    const int r1 = 2 * Yc + 1 < a.H ? a.W_ : 0;  // row 2Y+1, or row 2Y again
+    const int r1 = 2 * Yc + 1 < a.H ? a.W : 0;  // row 2Y+1, or row 2Y again
     const int p1 = 2 * c + 1 < a.D ? hplane : 0;  // plane 2c+1, or plane 2c again
     const T* p = hin + 2 * c * hplane;
     e1 = ld16(p + ho_own + r1);
@@ -401,7 +389,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
     code(5, pY, e1, 0, oY);
     code(2, pF, e1, 1, oF);
     if constexpr (DEC) {
-      if (vy1) st16(h0 + a.W_, pack16<T, VX>(oY, oF));  // plane 2c, row 2Y+1: Y | FB
+      if (vy1) st16(h0 + a.W, pack16<T, VX>(oY, oF));  // plane 2c, row 2Y+1: Y | FB
     } else {
       put8(5, oY);
       put8(2, oF);
@@ -444,7 +432,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
     code(0, pL, o1, 0, oL);
     code(3, pC, o1, 1, oC);
     if constexpr (DEC) {
-      if (vz1 && vy1) st16(h0 + hplane + a.W_, pack16<T, VX>(oL, oC));  // plane 2c+1, row 2Y+1: LR | C
+      if (vz1 && vy1) st16(h0 + hplane + a.W, pack16<T, VX>(oL, oC));  // plane 2c+1, row 2Y+1: LR | C
     } else {
       put8(0, oL);
       put8(3, oC);
@@ -491,13 +479,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
   constexpr int G = VX / 4;
   constexpr uint32_t MASK = sizeof(T) == 2 ? 0xffffu : 0xffu;
   using V = typename std::conditional<DEC, uint2, uint4>::type;
-  const CFloat Wc = (CFloat)a.W, Bc = (CFloat)a.b;
+  const CFloat Wc = (CFloat)a.wt, Bc = (CFloat)a.b;
 
   const int lane = threadIdx.x;
   const int tx = lane & (a.txn - 1);
   const int r = lane >> __builtin_ctz(a.txn);
   const int rows = a.rows;
   const int X = tx * VX;
+  // xcd_block (kmp_wave.h), spelled out: with the call the compiler orders this kernel's encode
+  // instructions differently (the same instructions), and its tuning was measured on this order
   int blk = (int)blockIdx.x;
   if (a.xcd_per > 0) {
     const int x = blk % 8, k = blk / 8;
@@ -514,7 +504,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
   const CFloat WcQ0 = !vz0 ? Zc : Wc, BcQ0 = !vz0 ? Zc + 152 : Bc;
   const int adn = ((lane + a.txn) & 63) << 2, aup = ((lane - a.txn) & 63) << 2;
 
-  const int hplane = a.H * a.W_;
+  const int hplane = a.H * a.W;
   const int lplane = a.Ey * a.Ex;
   const int hx = 2 * X;
   // Addresses: a uniform (scalar) base per row stream plus ONE 32-bit lane offset per layout, so the
@@ -522,11 +512,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
   // and no per-stream 64-bit pointers occupy vector registers.  Node rows of node planes c-1, c,
   // c+1: a lowres row is one row of the decode's lowres / two rows of the encode's highres.
   constexpr int SZ = (int)sizeof(T);
-  const int nstride = DEC ? a.Ex : 2 * a.W_;  // elements per lowres row in the node planes
+  const int nstride = DEC ? a.Ex : 2 * a.W;  // elements per lowres row in the node planes
   const uint32_t lon = (uint32_t)((r * nstride + (DEC ? X : hx)) * SZ);  // node / stream / highres rows
   const uint32_t lonx = (uint32_t)((DEC ? X : hx) * SZ);                 // the same at row 0
   const uint32_t lom = (uint32_t)((r * a.Ex + X) * SZ);                  // lowres / map rows
-  const uint32_t loh = (uint32_t)((2 * r * a.W_ + hx) * SZ);             // highres rows (the decode's output)
+  const uint32_t loh = (uint32_t)((2 * r * a.W + hx) * SZ);             // highres rows (the decode's output)
   const char* un[3];
 #pragma unroll
   for (int t = 0; t < 3; ++t) {
@@ -551,7 +541,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
   }
   char* ulo = DEC ? nullptr : (char*)a.lo_out + (b * a.Ez + c) * (int64_t)lplane * SZ;
   char* uho = DEC ? (char*)a.hi_out + (b * a.D + 2 * c) * (int64_t)hplane * SZ : nullptr;
-  const int nstep = rows * nstride * SZ, mstep = rows * a.Ex * SZ, hstep = rows * 2 * a.W_ * SZ;
+  const int nstep = rows * nstride * SZ, mstep = rows * a.Ex * SZ, hstep = rows * 2 * a.W * SZ;
 
   // node rows: a ring of three steps -- the current one, the next (its first row is the current
   // last row's row below) and the one after, in flight; stream / map rows: the next step's in flight
@@ -575,7 +565,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
       for (int k = 0; k < 7; ++k) om[k] = ld8(um[k] + s * mstep + lom);
     } else {
       const char* p = us + s * hstep;
-      const int rw = a.W_ * SZ;
+      const int rw = a.W * SZ;
       os[0] = ld16(p + rw + lon);
       os[1] = ld16(p + p1 + lon);
       os[2] = ld16(p + p1 + rw + lon);
@@ -763,7 +753,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
       code(5, pY, e1, 0, oY);
       code(2, pF, e1, 1, oF);
       if constexpr (DEC) {
-        st16(h0 + a.W_ * SZ + loh, pack16<T, VX>(oY, oF));  // plane 2c, row 2Y+1: Y | FB
+        st16(h0 + a.W * SZ + loh, pack16<T, VX>(oY, oF));  // plane 2c, row 2Y+1: Y | FB
       } else {
         put8(5, oY);
         put8(2, oF);
@@ -784,7 +774,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
       code(0, pL, o1, 0, oL);
       code(3, pC, o1, 1, oC);
       if constexpr (DEC) {
-        if (vz1) st16(h0 + (hplane + a.W_) * SZ + loh, pack16<T, VX>(oL, oC));  // plane 2c+1, row 2Y+1: LR | C
+        if (vz1) st16(h0 + (hplane + a.W) * SZ + loh, pack16<T, VX>(oL, oC));  // plane 2c+1, row 2Y+1: LR | C
       } else {
         put8(0, oL);
         put8(3, oC);
@@ -825,7 +815,6 @@ template <typename T>
 static bool linear3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred,
                               const kmp_region* region, l3::L3& a, dim3& grid, dim3& block, size_t& lds) {
   constexpr int VX = 8 / (int)sizeof(T);
-  if (!(std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value)) return false;
   if (opt(OPT_DISABLE_FAST, 0) || opt(OPT_DISABLE_LINEAR_FUSED, 0)) return false;
   if (C != 1 || pred->kind != KMP_PRED_LINEAR || pred->padding != 0) return false;
   if (g.n[2] % 2 != 0 || (g.n[2] * (int64_t)sizeof(T)) % 16 != 0) return false;
@@ -835,21 +824,13 @@ static bool linear3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_pred
   const int64_t rows = 64 / txn;
   const int64_t waves = ceil_div(g.E[1], rows);
   const bool tall = waves > 4;  // the plane-block workgroup covers the whole plane (row exchange through LDS)
-  int64_t zb = 0, ze = g.E[0];
-  if (region) {
-    if (region->begin[1] > 0 || region->begin[2] > 0 || region->end[1] < g.E[1] || region->end[2] < g.E[2]) return false;
-    zb = region->begin[0] < 0 ? 0 : region->begin[0];
-    ze = region->end[0] > g.E[0] ? g.E[0] : region->end[0];
-    if (ze <= zb) return false;
-  }
-  a.D = (int)g.n[0]; a.H = (int)g.n[1]; a.W_ = (int)g.n[2];
-  a.Lz = (int)g.L[0]; a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
-  a.Ez = (int)g.E[0]; a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcz = (int)g.Lc[0]; a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  int64_t zb, ze;
+  if (!region_span(region, g, 0, zb, ze)) return false;
+  set_extents<3>(a, g);
   a.zbegin = (int)zb; a.zend = (int)ze;
   a.txn = (int)txn; a.rows = (int)rows; a.nwv = (int)waves;
   const int64_t nblk = B * (ze - zb);
-  a.xcd_per = (opt(OPT_W3_XCD, 1) && B % 8 == 0) ? (int)(ze - zb) : 0;
+  a.xcd_per = xcd_per_tile(OPT_W3_XCD, B, ze - zb);
   a.full = g.Lc[1] == g.E[1] && g.Lc[2] == g.E[2];
   lds = (size_t)(waves * l3::kXch * g.E[2]) * sizeof(uint32_t);
   grid = dim3((unsigned)nblk);
@@ -858,81 +839,37 @@ static bool linear3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_pred
   return nblk < ((int64_t)1 << 31);
 }
 
-template <typename T>
-int try_linear3d_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                        const MapPtrs& maps, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    l3::L3 a{};
-    dim3 grid, block;
-    size_t lds = 0;
-    if (!linear3d_geometry<T>(g, B, C, pred, region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k)
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    a.W = pred->weights;
-    a.b = pred->bias;
-    if (const int steps = l3y_steps(a)) {
-      const dim3 g1(grid.x), b1(64);  // one wave per output plane
-      const size_t xl = (size_t)(a.rows + 1) * a.txn * l3::kXch * (8 / sizeof(T)) * 4;  // the row ring
-      if (steps == 1) l3::linear3y_kernel<T, false, 1, L3Y_WPE><<<g1, b1, xl, stream>>>(a);
-      else if (steps == 2) l3::linear3y_kernel<T, false, 2, L3Y_WPE><<<g1, b1, xl, stream>>>(a);
-      else if (steps == 4) l3::linear3y_kernel<T, false, 4, L3Y_WPE><<<g1, b1, xl, stream>>>(a);
-      else l3::linear3y_kernel<T, false, 8, (sizeof(T) == 2 ? 3 : 2)><<<g1, b1, xl, stream>>>(a);
-      return check_launch("linear3y_encode");
-    }
-    if (a.full) l3::linear3d_kernel<T, false, true, 5><<<grid, block, lds, stream>>>(a);
-    else l3::linear3d_kernel<T, false, false, 1><<<grid, block, lds, stream>>>(a);
-    return check_launch("linear3d_encode");
+template <typename T, bool DEC>
+int try_linear3d(const CodecCall<T, DEC>& c) {
+  l3::L3 a{};
+  dim3 grid, block;
+  size_t lds = 0;
+  if (!linear3d_geometry<T>(c.g, c.B, c.C, c.pred, c.region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 16, 8, 7)) return KMP_ERR_UNSUPPORTED;
+  bind(a, c);
+  a.wt = c.pred->weights;
+  a.b = c.pred->bias;
+  if constexpr (DEC) a.uld = a.Lcz > 0 && a.Lcy > 0;  // clamped map planes / rows exist
+  if (const int steps = l3y_steps(a)) {
+    const dim3 g1(grid.x), b1(64);  // one wave per output plane
+    const size_t xl = (size_t)(a.rows + 1) * a.txn * l3::kXch * (8 / sizeof(T)) * 4;  // the row ring
+    if (steps == 1) l3::linear3y_kernel<T, DEC, 1, L3Y_WPE><<<g1, b1, xl, c.stream>>>(a);
+    else if (steps == 2) l3::linear3y_kernel<T, DEC, 2, L3Y_WPE><<<g1, b1, xl, c.stream>>>(a);
+    else if (steps == 4) l3::linear3y_kernel<T, DEC, 4, L3Y_WPE><<<g1, b1, xl, c.stream>>>(a);
+    else l3::linear3y_kernel<T, DEC, 8, (sizeof(T) == 2 ? 3 : 2)><<<g1, b1, xl, c.stream>>>(a);
+    return check_launch(DEC ? "linear3y_decode" : "linear3y_encode");
   }
-  return KMP_ERR_UNSUPPORTED;
+  if constexpr (DEC) {
+    if (a.full && a.uld) l3::linear3d_kernel<T, true, true, 5, true><<<grid, block, lds, c.stream>>>(a);
+    else if (a.full) l3::linear3d_kernel<T, true, true, 5><<<grid, block, lds, c.stream>>>(a);
+    else l3::linear3d_kernel<T, true, false, 1><<<grid, block, lds, c.stream>>>(a);
+  } else {
+    if (a.full) l3::linear3d_kernel<T, false, true, 5><<<grid, block, lds, c.stream>>>(a);
+    else l3::linear3d_kernel<T, false, false, 1><<<grid, block, lds, c.stream>>>(a);
+  }
+  return check_launch(DEC ? "linear3d_decode" : "linear3d_encode");
 }
 
-template <typename T>
-int try_linear3d_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                        const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    l3::L3 a{};
-    dim3 grid, block;
-    size_t lds = 0;
-    if (!linear3d_geometry<T>(g, B, C, pred, region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k) {
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    a.W = pred->weights;
-    a.b = pred->bias;
-    a.uld = a.Lcz > 0 && a.Lcy > 0;  // clamped map planes / rows exist
-    if (const int steps = l3y_steps(a)) {
-      const dim3 g1(grid.x), b1(64);  // one wave per output plane
-      const size_t xl = (size_t)(a.rows + 1) * a.txn * l3::kXch * (8 / sizeof(T)) * 4;  // the row ring
-      if (steps == 1) l3::linear3y_kernel<T, true, 1, L3Y_WPE><<<g1, b1, xl, stream>>>(a);
-      else if (steps == 2) l3::linear3y_kernel<T, true, 2, L3Y_WPE><<<g1, b1, xl, stream>>>(a);
-      else if (steps == 4) l3::linear3y_kernel<T, true, 4, L3Y_WPE><<<g1, b1, xl, stream>>>(a);
-      else l3::linear3y_kernel<T, true, 8, (sizeof(T) == 2 ? 3 : 2)><<<g1, b1, xl, stream>>>(a);
-      return check_launch("linear3y_decode");
-    }
-    if (a.full && a.uld) l3::linear3d_kernel<T, true, true, 5, true><<<grid, block, lds, stream>>>(a);
-    else if (a.full) l3::linear3d_kernel<T, true, true, 5><<<grid, block, lds, stream>>>(a);
-    else l3::linear3d_kernel<T, true, false, 1><<<grid, block, lds, stream>>>(a);
-    return check_launch("linear3d_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_L3_INST(T)                                                                                    \
-  template int try_linear3d_encode<T>(const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,   \
-                                      const MapPtrs&, const kmp_region*, hipStream_t);                    \
-  template int try_linear3d_decode<T>(const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,            \
-                                      const kmp_predictor*, T*, const kmp_region*, hipStream_t);
-KMP_L3_INST(uint8_t)
-KMP_L3_INST(uint16_t)
-KMP_L3_INST(int32_t)
-KMP_L3_INST(uint32_t)
+KMP_INST_FAMILY_U8_U16(try_linear3d)
 
 }  // namespace kmp

@@ -45,10 +45,10 @@ struct L3P {
   const void* lo_in;
   void* lo_out;
   MapPtrs maps;
-  const float* W;  // [N, 19] row-major
-  const float* b;  // [19]
-  const float* Wr; // the weights reordered per sweep (linear_reorder_kernel), in the workspace
-  int32_t D, H, W_;
+  const float* wt;  // [N, 19] row-major
+  const float* b;   // [19]
+  const float* Wr;  // the weights reordered per sweep (linear_reorder_kernel), in the workspace
+  int32_t D, H, W;
   int32_t Lz, Ly, Lx, Ez, Ey, Ex, Lcz, Lcy, Lcx;
   int32_t zbegin, zend;
   int32_t txn, rows, nwv;
@@ -161,11 +161,7 @@ __global__ void __launch_bounds__(256) linear3dp_kernel(L3P a) {
   const int tx = lane & (a.txn - 1);
   const int r = lane >> __builtin_ctz(a.txn);
   const int X = tx * VX;
-  int blk = (int)blockIdx.x;
-  if (a.xcd_per > 0) {
-    const int x = blk % 8, k = blk / 8;
-    blk = ((k / a.xcd_per) * 8 + x) * a.xcd_per + (k % a.xcd_per);
-  }
+  int blk = xcd_block((int)blockIdx.x, a.xcd_per);
   const int nplanes = a.zend - a.zbegin;
   const int c = a.zbegin + blk % nplanes;
   const int64_t b = blk / nplanes;
@@ -179,13 +175,13 @@ __global__ void __launch_bounds__(256) linear3dp_kernel(L3P a) {
   const bool vy0 = Y >= 1;
   const bool vz1 = c < a.Lcz, vz0 = c >= 1;
 
-  const int hplane = a.H * a.W_;
+  const int hplane = a.H * a.W;
   const int lplane = a.Ey * a.Ex;
   const T* hin = DEC ? nullptr : (const T*)a.hi_in + b * (int64_t)a.D * hplane;
   T* hout = DEC ? (T*)a.hi_out + b * (int64_t)a.D * hplane : nullptr;
   const T* lin = DEC ? (const T*)a.lo_in + b * (int64_t)a.Ez * lplane : nullptr;
   const int hx = 2 * X;
-  const int ho_own = 2 * Yc * a.W_ + hx;
+  const int ho_own = 2 * Yc * a.W + hx;
   const int lo_own = Yc * a.Ex + X;
 
   const T* mbase[7];
@@ -225,9 +221,9 @@ __global__ void __launch_bounds__(256) linear3dp_kernel(L3P a) {
     }
   } else {
     const T* p = hin + 2 * c * hplane;
-    if (live && vy1) e1 = ldH<T>(p + ho_own + a.W_);
+    if (live && vy1) e1 = ldH<T>(p + ho_own + a.W);
     if (live && vz1) o0 = ldH<T>(p + hplane + ho_own);
-    if (live && vz1 && vy1) o1 = ldH<T>(p + hplane + ho_own + a.W_);
+    if (live && vz1 && vy1) o1 = ldH<T>(p + hplane + ho_own + a.W);
   }
 
   // ---- stage: every lane writes its 4 nodes of each plane, plus the mirrored halo columns /
@@ -378,7 +374,7 @@ __global__ void __launch_bounds__(256) linear3dp_kernel(L3P a) {
     code(5, pY, e1, 0, oY);
     code(2, pF, e1, 1, oF);
     if constexpr (DEC) {
-      if (vy1) stH<T>(h0 + a.W_, packH<T>(oY, oF));
+      if (vy1) stH<T>(h0 + a.W, packH<T>(oY, oF));
     } else {
       put8(5, oY);
       put8(2, oF);
@@ -413,7 +409,7 @@ __global__ void __launch_bounds__(256) linear3dp_kernel(L3P a) {
     code(0, pL, o1, 0, oL);
     code(3, pC, o1, 1, oC);
     if constexpr (DEC) {
-      if (vz1 && vy1) stH<T>(h0 + hplane + a.W_, packH<T>(oL, oC));
+      if (vz1 && vy1) stH<T>(h0 + hplane + a.W, packH<T>(oL, oC));
     } else {
       put8(0, oL);
       put8(3, oC);
@@ -431,7 +427,6 @@ template <typename T>
 static bool linear3dp_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred,
                                const kmp_region* region, l3p::L3P& a, dim3& grid, dim3& block, size_t& lds) {
   constexpr int VX = 4;
-  if (!std::is_same<T, uint16_t>::value && !std::is_same<T, uint8_t>::value) return false;
   if (opt(OPT_DISABLE_FAST, 0) || opt(OPT_DISABLE_LINEAR_FUSED, 0)) return false;
   if (C != 1 || pred->kind != KMP_PRED_LINEAR || pred->padding != 1 || !pred->weights || !pred->bias) return false;
   const int P = pred->padding;
@@ -444,17 +439,9 @@ static bool linear3dp_geometry(const Geo& g, int64_t B, int64_t C, const kmp_pre
   if (waves > 4) return false;  // the workgroup covers the whole plane (row exchange through LDS)
   // one reflection covers every halo index (lsrc1): L >= P + 2 on each axis
   if (g.L[0] < P + 2 || g.L[1] < P + 2 || g.L[2] < P + 2) return false;
-  int64_t zb = 0, ze = g.E[0];
-  if (region) {
-    if (region->begin[1] > 0 || region->begin[2] > 0 || region->end[1] < g.E[1] || region->end[2] < g.E[2]) return false;
-    zb = region->begin[0] < 0 ? 0 : region->begin[0];
-    ze = region->end[0] > g.E[0] ? g.E[0] : region->end[0];
-    if (ze <= zb) return false;
-  }
-  a.D = (int)g.n[0]; a.H = (int)g.n[1]; a.W_ = (int)g.n[2];
-  a.Lz = (int)g.L[0]; a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
-  a.Ez = (int)g.E[0]; a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcz = (int)g.Lc[0]; a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  int64_t zb, ze;
+  if (!region_span(region, g, 0, zb, ze)) return false;
+  set_extents<3>(a, g);
   a.zbegin = (int)zb; a.zend = (int)ze;
   a.txn = (int)txn; a.rows = (int)rows; a.nwv = (int)waves;
   // staged rows: node rows -P .. Ey+P (every row a lane's neighbourhood reads); columns: node
@@ -465,77 +452,30 @@ static bool linear3dp_geometry(const Geo& g, int64_t B, int64_t C, const kmp_pre
   lds = (size_t)(npl * a.nr * a.pitch + waves * l3p::kXch * g.E[2]) * sizeof(uint32_t);
   if (lds > 64 * 1024) return false;
   const int64_t nblk = B * (ze - zb);
-  a.xcd_per = (opt(OPT_W3_XCD, 1) && B % 8 == 0) ? (int)(ze - zb) : 0;
+  a.xcd_per = xcd_per_tile(OPT_W3_XCD, B, ze - zb);
   grid = dim3((unsigned)nblk);
   block = dim3((unsigned)(64 * waves));
   return nblk < ((int64_t)1 << 31);
 }
 
-template <typename T>
-int try_linear3dp_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                         const MapPtrs& maps, const kmp_region* region, void* ws, size_t ws_bytes,
-                         hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    l3p::L3P a{};
-    dim3 grid, block;
-    size_t lds = 0;
-    if (!linear3dp_geometry<T>(g, B, C, pred, region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
-    constexpr uintptr_t HA = 8 * sizeof(T) - 1, MA = 4 * sizeof(T) - 1;  // segment alignments
-    if (((uintptr_t)hi & HA) || ((uintptr_t)lowres & MA)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k)
-      if ((uintptr_t)maps.p[k] & MA) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    a.W = pred->weights;
-    a.b = pred->bias;
-    if (!ws || ws_bytes < kL3pWsBytes) return KMP_ERR_UNSUPPORTED;
-    a.Wr = (const float*)ws;
-    l3p::linear_reorder_kernel<<<1, 256, 0, stream>>>(pred->weights, (float*)ws, 4);
-    if (a.Lcy == a.Ey && a.Lcx == a.Ex) l3p::linear3dp_kernel<T, false, 1, true><<<grid, block, lds, stream>>>(a);
-    else l3p::linear3dp_kernel<T, false, 1, false><<<grid, block, lds, stream>>>(a);
-    return check_launch("linear3dp_encode");
-  }
-  return KMP_ERR_UNSUPPORTED;
+template <typename T, bool DEC>
+int try_linear3dp(const CodecCall<T, DEC>& c) {
+  l3p::L3P a{};
+  dim3 grid, block;
+  size_t lds = 0;
+  if (!linear3dp_geometry<T>(c.g, c.B, c.C, c.pred, c.region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 8 * sizeof(T), 4 * sizeof(T), 7)) return KMP_ERR_UNSUPPORTED;  // segment alignments
+  bind(a, c);
+  a.wt = c.pred->weights;
+  a.b = c.pred->bias;
+  if (!c.ws || c.ws_bytes < kL3pWsBytes) return KMP_ERR_UNSUPPORTED;
+  a.Wr = (const float*)c.ws;
+  l3p::linear_reorder_kernel<<<1, 256, 0, c.stream>>>(c.pred->weights, (float*)c.ws, 4);
+  if (a.Lcy == a.Ey && a.Lcx == a.Ex) l3p::linear3dp_kernel<T, DEC, 1, true><<<grid, block, lds, c.stream>>>(a);
+  else l3p::linear3dp_kernel<T, DEC, 1, false><<<grid, block, lds, c.stream>>>(a);
+  return check_launch(DEC ? "linear3dp_decode" : "linear3dp_encode");
 }
 
-template <typename T>
-int try_linear3dp_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                         const kmp_predictor* pred, T* hi, const kmp_region* region, void* ws, size_t ws_bytes,
-                         hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    l3p::L3P a{};
-    dim3 grid, block;
-    size_t lds = 0;
-    if (!linear3dp_geometry<T>(g, B, C, pred, region, a, grid, block, lds)) return KMP_ERR_UNSUPPORTED;
-    constexpr uintptr_t HA = 8 * sizeof(T) - 1, MA = 4 * sizeof(T) - 1;
-    if (((uintptr_t)hi & HA) || ((uintptr_t)lowres & MA)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k) {
-      if ((uintptr_t)maps.p[k] & MA) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    a.W = pred->weights;
-    a.b = pred->bias;
-    if (!ws || ws_bytes < kL3pWsBytes) return KMP_ERR_UNSUPPORTED;
-    a.Wr = (const float*)ws;
-    l3p::linear_reorder_kernel<<<1, 256, 0, stream>>>(pred->weights, (float*)ws, 4);
-    if (a.Lcy == a.Ey && a.Lcx == a.Ex) l3p::linear3dp_kernel<T, true, 1, true><<<grid, block, lds, stream>>>(a);
-    else l3p::linear3dp_kernel<T, true, 1, false><<<grid, block, lds, stream>>>(a);
-    return check_launch("linear3dp_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_L3P_INST(T)                                                                                   \
-  template int try_linear3dp_encode<T>(const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,  \
-                                       const MapPtrs&, const kmp_region*, void*, size_t, hipStream_t);    \
-  template int try_linear3dp_decode<T>(const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,           \
-                                       const kmp_predictor*, T*, const kmp_region*, void*, size_t, hipStream_t);
-KMP_L3P_INST(uint8_t)
-KMP_L3P_INST(uint16_t)
-KMP_L3P_INST(int32_t)
-KMP_L3P_INST(uint32_t)
+KMP_INST_FAMILY_U8_U16(try_linear3dp)
 
 }  // namespace kmp

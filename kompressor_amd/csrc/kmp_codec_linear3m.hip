@@ -37,9 +37,9 @@ struct M3 {
   const void* lo_in;
   void* lo_out;
   MapPtrs maps;
-  const float* W;  // [8, 19] row-major
-  const float* b;  // [19]
-  int32_t D, H, W_;
+  const float* wt;  // [8, 19] row-major
+  const float* b;   // [19]
+  int32_t D, H, W;
   int32_t Lz, Ly, Lx, Ez, Ey, Ex, Lcz, Lcy, Lcx;
   int32_t zbegin, zend;
   int32_t xcd_per;
@@ -92,11 +92,7 @@ __global__ void __launch_bounds__(64) linear3m_kernel(M3 a) {
   const int r = lane / TXN;
   const int X = tx * VX;
   const int m = lane & 15, g = lane >> 4;  // MFMA roles: column / cell m, lane group g
-  int blk = (int)blockIdx.x;
-  if (a.xcd_per > 0) {
-    const int x = blk % 8, k = blk / 8;
-    blk = ((k / a.xcd_per) * 8 + x) * a.xcd_per + (k % a.xcd_per);
-  }
+  int blk = xcd_block((int)blockIdx.x, a.xcd_per);
   const int nplanes = a.zend - a.zbegin;
   const int c = a.zbegin + blk % nplanes;
   const int64_t b = blk / nplanes;
@@ -108,18 +104,18 @@ __global__ void __launch_bounds__(64) linear3m_kernel(M3 a) {
   // the tile gets zero weights and bias: its channels are 0, as the aggregation's masks want ----
   const int chP = kPch[m], chQ = kQch[m];
   const bool okP = chP >= 0 && vz1, okQ = chQ >= 0 && vz0;
-  const bx::u32x4 bP = bx::b_fragment(a.W + (chP >= 0 ? chP : 0), 19, 8, 3, 0, 0, g, okP);
-  const bx::u32x4 bQ = bx::b_fragment(a.W + (chQ >= 0 ? chQ : 0), 19, 8, 3, 0, 0, g, okQ);
+  const bx::u32x4 bP = bx::b_fragment(a.wt + (chP >= 0 ? chP : 0), 19, 8, 3, 0, 0, g, okP);
+  const bx::u32x4 bQ = bx::b_fragment(a.wt + (chQ >= 0 ? chQ : 0), 19, 8, 3, 0, 0, g, okQ);
   const float biasP = okP ? a.b[chP] : 0.0f, biasQ = okQ ? a.b[chQ] : 0.0f;
 
-  const int hplane = a.H * a.W_;
+  const int hplane = a.H * a.W;
   const int lplane = a.Ey * EX;
   const int hx = 2 * X;
-  const int nstride = DEC ? EX : 2 * a.W_;
+  const int nstride = DEC ? EX : 2 * a.W;
   const uint32_t lon = (uint32_t)((r * nstride + (DEC ? X : hx)) * SZ);
   const uint32_t lonx = (uint32_t)((DEC ? X : hx) * SZ);
   const uint32_t lom = (uint32_t)((r * EX + X) * SZ);
-  const uint32_t loh = (uint32_t)((2 * r * a.W_ + hx) * SZ);
+  const uint32_t loh = (uint32_t)((2 * r * a.W + hx) * SZ);
   const char* un[3];
 #pragma unroll
   for (int t = 0; t < 3; ++t) {
@@ -141,7 +137,7 @@ __global__ void __launch_bounds__(64) linear3m_kernel(M3 a) {
   }
   char* ulo = DEC ? nullptr : (char*)a.lo_out + (b * a.Ez + c) * (int64_t)lplane * SZ;
   char* uho = DEC ? (char*)a.hi_out + (b * a.D + 2 * c) * (int64_t)hplane * SZ : nullptr;
-  const int nstep = ROWS * nstride * SZ, mstep = ROWS * EX * SZ, hstep = ROWS * 2 * a.W_ * SZ;
+  const int nstep = ROWS * nstride * SZ, mstep = ROWS * EX * SZ, hstep = ROWS * 2 * a.W * SZ;
 
   V cur[3], nxt[3], nx2[3];
   uint4 cs[3], ns[3];
@@ -162,7 +158,7 @@ __global__ void __launch_bounds__(64) linear3m_kernel(M3 a) {
       for (int k = 0; k < 7; ++k) om[k] = ld8(um[k] + s * mstep + lom);
     } else {
       const char* p = us + s * hstep;
-      const int rw = a.W_ * SZ;
+      const int rw = a.W * SZ;
       os[0] = ld16(p + rw + lon);
       os[1] = ld16(p + p1 + lon);
       os[2] = ld16(p + p1 + rw + lon);
@@ -364,7 +360,7 @@ __global__ void __launch_bounds__(64) linear3m_kernel(M3 a) {
       code(5, pY, e1, 0, oY);
       code(2, pF, e1, 1, oF);
       if constexpr (DEC) {
-        st16(h0 + a.W_ * SZ + loh, pack16<T, VX>(oY, oF));
+        st16(h0 + a.W * SZ + loh, pack16<T, VX>(oY, oF));
       } else {
         put8(5, oY);
         put8(2, oF);
@@ -387,7 +383,7 @@ __global__ void __launch_bounds__(64) linear3m_kernel(M3 a) {
       code(0, pL, o1, 0, oL);
       code(3, pC, o1, 1, oC);
       if constexpr (DEC) {
-        if (vz1) st16(h0 + (hplane + a.W_) * SZ + loh, pack16<T, VX>(oL, oC));
+        if (vz1) st16(h0 + (hplane + a.W) * SZ + loh, pack16<T, VX>(oL, oC));
       } else {
         put8(0, oL);
         put8(3, oC);
@@ -414,7 +410,6 @@ template <typename T>
 static bool linear3m_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, const kmp_region* region,
                               l3m::M3& a, int& steps, dim3& grid) {
   constexpr int VX = 8 / (int)sizeof(T);
-  if (!(std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value)) return false;
   if (opt(OPT_DISABLE_FAST, 0) || opt(OPT_DISABLE_LINEAR_FUSED, 0)) return false;
   if (C != 1 || pred->kind != KMP_PRED_LINEAR_MFMA || pred->padding != 0 || !pred->weights || !pred->bias) return false;
   if (g.Lc[1] != g.E[1] || g.Lc[2] != g.E[2] || g.Lc[0] < 1) return false;
@@ -426,20 +421,12 @@ static bool linear3m_geometry(const Geo& g, int64_t B, int64_t C, const kmp_pred
   if (g.E[1] % rows != 0) return false;
   steps = (int)(g.E[1] / rows);
   if (steps != 1 && steps != 2 && steps != 4) return false;
-  int64_t zb = 0, ze = g.E[0];
-  if (region) {
-    if (region->begin[1] > 0 || region->begin[2] > 0 || region->end[1] < g.E[1] || region->end[2] < g.E[2]) return false;
-    zb = region->begin[0] < 0 ? 0 : region->begin[0];
-    ze = region->end[0] > g.E[0] ? g.E[0] : region->end[0];
-    if (ze <= zb) return false;
-  }
-  a.D = (int)g.n[0]; a.H = (int)g.n[1]; a.W_ = (int)g.n[2];
-  a.Lz = (int)g.L[0]; a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
-  a.Ez = (int)g.E[0]; a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcz = (int)g.Lc[0]; a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  int64_t zb, ze;
+  if (!region_span(region, g, 0, zb, ze)) return false;
+  set_extents<3>(a, g);
   a.zbegin = (int)zb; a.zend = (int)ze;
   const int64_t nblk = B * (ze - zb);
-  a.xcd_per = (opt(OPT_W3_XCD, 1) && B % 8 == 0) ? (int)(ze - zb) : 0;
+  a.xcd_per = xcd_per_tile(OPT_W3_XCD, B, ze - zb);
   grid = dim3((unsigned)nblk);
   return nblk < ((int64_t)1 << 31);
 }
@@ -460,59 +447,20 @@ static void launch_linear3m(int ex, int steps, dim3 grid, hipStream_t stream, co
 #undef KMP_L3M
 }
 
-template <typename T>
-int try_linear3m_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                        const MapPtrs& maps, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    l3m::M3 a{};
-    int steps = 0;
-    dim3 grid;
-    if (!linear3m_geometry<T>(g, B, C, pred, region, a, steps, grid)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k)
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    a.W = pred->weights;
-    a.b = pred->bias;
-    launch_linear3m<T, false>(a.Ex, steps, grid, stream, a);
-    return check_launch("linear3m_encode");
-  }
-  return KMP_ERR_UNSUPPORTED;
+template <typename T, bool DEC>
+int try_linear3m(const CodecCall<T, DEC>& c) {
+  l3m::M3 a{};
+  int steps = 0;
+  dim3 grid;
+  if (!linear3m_geometry<T>(c.g, c.B, c.C, c.pred, c.region, a, steps, grid)) return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 16, 8, 7)) return KMP_ERR_UNSUPPORTED;
+  bind(a, c);
+  a.wt = c.pred->weights;
+  a.b = c.pred->bias;
+  launch_linear3m<T, DEC>(a.Ex, steps, grid, c.stream, a);
+  return check_launch(DEC ? "linear3m_decode" : "linear3m_encode");
 }
 
-template <typename T>
-int try_linear3m_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                        const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    l3m::M3 a{};
-    int steps = 0;
-    dim3 grid;
-    if (!linear3m_geometry<T>(g, B, C, pred, region, a, steps, grid)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k) {
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    a.W = pred->weights;
-    a.b = pred->bias;
-    launch_linear3m<T, true>(a.Ex, steps, grid, stream, a);
-    return check_launch("linear3m_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_L3M_INST(T)                                                                                   \
-  template int try_linear3m_encode<T>(const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,   \
-                                      const MapPtrs&, const kmp_region*, hipStream_t);                    \
-  template int try_linear3m_decode<T>(const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,            \
-                                      const kmp_predictor*, T*, const kmp_region*, hipStream_t);
-KMP_L3M_INST(uint8_t)
-KMP_L3M_INST(uint16_t)
-KMP_L3M_INST(int32_t)
-KMP_L3M_INST(uint32_t)
+KMP_INST_FAMILY_U8_U16(try_linear3m)
 
 }  // namespace kmp

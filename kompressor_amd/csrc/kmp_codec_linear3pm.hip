@@ -59,9 +59,9 @@ struct PM {
   const void* lo_in;
   void* lo_out;
   MapPtrs maps;
-  const float* W;  // [64, 19] row-major
-  const float* b;  // [19]
-  int32_t D, H, W_;
+  const float* wt;  // [64, 19] row-major
+  const float* b;   // [19]
+  int32_t D, H, W;
   int32_t Lz, Ly, Lx, Ez, Ey, Ex, Lcz, Lcy, Lcx;
   int32_t zbegin, zend;
   int32_t nsplit, zper;  // runs of output planes per tile, planes per run
@@ -157,11 +157,7 @@ __global__ void __launch_bounds__(64 * (EY / (256 / EX))) __attribute__((amdgpu_
   const int r = lane / TXN;
   const int X = tx * VX;
   const int m = lane & 15, g = lane >> 4;  // MFMA roles
-  int blk = (int)blockIdx.x;
-  if (a.xcd_per > 0) {
-    const int x = blk % 8, k = blk / 8;
-    blk = ((k / a.xcd_per) * 8 + x) * a.xcd_per + (k % a.xcd_per);
-  }
+  int blk = xcd_block((int)blockIdx.x, a.xcd_per);
   // the workgroup's tile and its run of output planes [cb, ce)
   const int64_t b = blk / a.nsplit;
   const int cb = a.zbegin + (blk % a.nsplit) * a.zper;
@@ -169,14 +165,14 @@ __global__ void __launch_bounds__(64 * (EY / (256 / EX))) __attribute__((amdgpu_
   const int Y0 = w * ROWS;
   const int Y = Y0 + r;
 
-  const int hplane = a.H * a.W_;
+  const int hplane = a.H * a.W;
   const int lplane = EY * EX;
   const T* hin = DEC ? nullptr : (const T*)a.hi_in + b * (int64_t)a.D * hplane;
   T* hout = DEC ? (T*)a.hi_out + b * (int64_t)a.D * hplane : nullptr;
   const T* lin = DEC ? (const T*)a.lo_in + b * (int64_t)a.Ez * lplane : nullptr;
   T* lout = DEC ? nullptr : (T*)a.lo_out + b * (int64_t)a.Ez * lplane;
   const int hx = 2 * X;
-  const int ho_own = 2 * Y * a.W_ + hx;
+  const int ho_own = 2 * Y * a.W + hx;
   const int lo_own = Y * EX + X;
   T* mbase[7];
 #pragma unroll
@@ -215,9 +211,9 @@ __global__ void __launch_bounds__(64 * (EY / (256 / EX))) __attribute__((amdgpu_
     } else {
       const T* p = hin + 2 * c * hplane;
       const int o = vz1 ? hplane : 0;
-      sv.e1 = ldH<T>(p + ho_own + a.W_);
+      sv.e1 = ldH<T>(p + ho_own + a.W);
       sv.o0 = ldH<T>(p + o + ho_own);
-      sv.o1 = ldH<T>(p + o + ho_own + a.W_);
+      sv.o1 = ldH<T>(p + o + ho_own + a.W);
     }
   };
 
@@ -507,7 +503,7 @@ __global__ void __launch_bounds__(64 * (EY / (256 / EX))) __attribute__((amdgpu_
 #pragma unroll
       for (int i = 0; i < VX; ++i) pF[i] = (P4[i + 1] + Q5[i + 1]) >> (nz >> 1);
       code(2, pF, sv.e1, 1, oF);
-      if constexpr (DEC) stH<T>(h0 + a.W_, packH<T>(keep, oF));
+      if constexpr (DEC) stH<T>(h0 + a.W, packH<T>(keep, oF));
       else put8(2, oF);
     }
     // LR map (1,1,0): ch0 (x), ch1 (x-1);  C (1,1,1): ch6
@@ -530,7 +526,7 @@ __global__ void __launch_bounds__(64 * (EY / (256 / EX))) __attribute__((amdgpu_
 #pragma unroll
       for (int i = 0; i < VX; ++i) pC[i] = P6[i + 1];
       code(3, pC, sv.o1, 1, oC);
-      if constexpr (DEC) stH<T>(vz1 ? h0 + hplane + a.W_ : dummy, packH<T>(keep, oC));
+      if constexpr (DEC) stH<T>(vz1 ? h0 + hplane + a.W : dummy, packH<T>(keep, oC));
       else put8(3, oC);
     }
   };
@@ -604,7 +600,6 @@ template <typename T>
 static bool linear3pm_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred,
                                const kmp_region* region, l3q::PM& a, dim3& grid, dim3& block) {
   constexpr int P = l3q::P;
-  if (!std::is_same<T, uint16_t>::value && !std::is_same<T, uint8_t>::value) return false;
   if (opt(OPT_DISABLE_FAST, 0) || opt(OPT_DISABLE_LINEAR_FUSED, 0)) return false;
   if (C != 1 || pred->kind != KMP_PRED_LINEAR_MFMA || pred->padding != P || !pred->weights || !pred->bias) return false;
   if (g.E[2] != 16 && g.E[2] != 32) return false;
@@ -614,17 +609,9 @@ static bool linear3pm_geometry(const Geo& g, int64_t B, int64_t C, const kmp_pre
   if (g.n[0] * g.n[1] * g.n[2] >= ((int64_t)1 << 31)) return false;
   // one reflection covers every halo index (lsrc1): L >= P + 2 on each axis
   if (g.L[0] < P + 2 || g.L[1] < P + 2 || g.L[2] < P + 2) return false;
-  int64_t zb = 0, ze = g.E[0];
-  if (region) {
-    if (region->begin[1] > 0 || region->begin[2] > 0 || region->end[1] < g.E[1] || region->end[2] < g.E[2]) return false;
-    zb = region->begin[0] < 0 ? 0 : region->begin[0];
-    ze = region->end[0] > g.E[0] ? g.E[0] : region->end[0];
-    if (ze <= zb) return false;
-  }
-  a.D = (int)g.n[0]; a.H = (int)g.n[1]; a.W_ = (int)g.n[2];
-  a.Lz = (int)g.L[0]; a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
-  a.Ez = (int)g.E[0]; a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcz = (int)g.Lc[0]; a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  int64_t zb, ze;
+  if (!region_span(region, g, 0, zb, ze)) return false;
+  set_extents<3>(a, g);
   a.zbegin = (int)zb; a.zend = (int)ze;
   // each workgroup codes a run of output planes of one tile (node planes staged once per run):
   // runs of >= 4 planes, enough of them for 2 workgroups per CU (the LDS holds 2)
@@ -634,7 +621,7 @@ static bool linear3pm_geometry(const Geo& g, int64_t B, int64_t C, const kmp_pre
   a.zper = (int)ceil_div(nz, nsplit);
   a.nsplit = (int)ceil_div(nz, a.zper);
   const int64_t nblk = B * a.nsplit;
-  a.xcd_per = (opt(OPT_W3_XCD, 1) && B % 8 == 0) ? a.nsplit : 0;
+  a.xcd_per = xcd_per_tile(OPT_W3_XCD, B, a.nsplit);
   const int rows = 64 / (a.Ex / 4);
   grid = dim3((unsigned)nblk);
   block = dim3((unsigned)(64 * (a.Ey / rows)));
@@ -654,67 +641,22 @@ static void launch_linear3pm(const l3q::PM& a, dim3 grid, dim3 block, hipStream_
 #undef KMP_L3Q
 }
 
-template <typename T>
-int try_linear3pm_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                         const MapPtrs& maps, const kmp_region* region, void* ws, size_t ws_bytes,
-                         hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    l3q::PM a{};
-    dim3 grid, block;
-    if (!linear3pm_geometry<T>(g, B, C, pred, region, a, grid, block)) return KMP_ERR_UNSUPPORTED;
-    constexpr uintptr_t HA = 8 * sizeof(T) - 1, MA = 4 * sizeof(T) - 1;  // segment alignments
-    if (((uintptr_t)hi & HA) || ((uintptr_t)lowres & MA)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k)
-      if ((uintptr_t)maps.p[k] & MA) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    a.W = pred->weights;
-    a.b = pred->bias;
-    if (!ws || ws_bytes < l3q::kWsBytes || ((uintptr_t)ws & 15)) return KMP_ERR_UNSUPPORTED;
-    a.frag = (const bx::u32x4*)ws;
-    l3q::fragments_kernel<<<l3q::kFragBlocks, 64, 0, stream>>>(pred->weights, pred->bias, (bx::u32x4*)ws);
-    launch_linear3pm<T, false>(a, grid, block, stream);
-    return check_launch("linear3pm_encode");
-  }
-  return KMP_ERR_UNSUPPORTED;
+template <typename T, bool DEC>
+int try_linear3pm(const CodecCall<T, DEC>& c) {
+  l3q::PM a{};
+  dim3 grid, block;
+  if (!linear3pm_geometry<T>(c.g, c.B, c.C, c.pred, c.region, a, grid, block)) return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 8 * sizeof(T), 4 * sizeof(T), 7)) return KMP_ERR_UNSUPPORTED;  // segment alignments
+  bind(a, c);
+  a.wt = c.pred->weights;
+  a.b = c.pred->bias;
+  if (!c.ws || c.ws_bytes < l3q::kWsBytes || ((uintptr_t)c.ws & 15)) return KMP_ERR_UNSUPPORTED;
+  a.frag = (const bx::u32x4*)c.ws;
+  l3q::fragments_kernel<<<l3q::kFragBlocks, 64, 0, c.stream>>>(c.pred->weights, c.pred->bias, (bx::u32x4*)c.ws);
+  launch_linear3pm<T, DEC>(a, grid, block, c.stream);
+  return check_launch(DEC ? "linear3pm_decode" : "linear3pm_encode");
 }
 
-template <typename T>
-int try_linear3pm_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                         const kmp_predictor* pred, T* hi, const kmp_region* region, void* ws, size_t ws_bytes,
-                         hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    l3q::PM a{};
-    dim3 grid, block;
-    if (!linear3pm_geometry<T>(g, B, C, pred, region, a, grid, block)) return KMP_ERR_UNSUPPORTED;
-    constexpr uintptr_t HA = 8 * sizeof(T) - 1, MA = 4 * sizeof(T) - 1;
-    if (((uintptr_t)hi & HA) || ((uintptr_t)lowres & MA)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k) {
-      if ((uintptr_t)maps.p[k] & MA) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    a.W = pred->weights;
-    a.b = pred->bias;
-    if (!ws || ws_bytes < l3q::kWsBytes || ((uintptr_t)ws & 15)) return KMP_ERR_UNSUPPORTED;
-    a.frag = (const bx::u32x4*)ws;
-    l3q::fragments_kernel<<<l3q::kFragBlocks, 64, 0, stream>>>(pred->weights, pred->bias, (bx::u32x4*)ws);
-    launch_linear3pm<T, true>(a, grid, block, stream);
-    return check_launch("linear3pm_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_L3Q_INST(T)                                                                                   \
-  template int try_linear3pm_encode<T>(const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,  \
-                                       const MapPtrs&, const kmp_region*, void*, size_t, hipStream_t);    \
-  template int try_linear3pm_decode<T>(const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,           \
-                                       const kmp_predictor*, T*, const kmp_region*, void*, size_t, hipStream_t);
-KMP_L3Q_INST(uint8_t)
-KMP_L3Q_INST(uint16_t)
-KMP_L3Q_INST(int32_t)
-KMP_L3Q_INST(uint32_t)
+KMP_INST_FAMILY_U8_U16(try_linear3pm)
 
 }  // namespace kmp

@@ -40,11 +40,6 @@ struct W2 {
   const float* bias;
 };
 
-template <typename T>
-__device__ __forceinline__ uint32_t cast_t(float v) {  // astype(T) for u8/u16: trunc, saturate, NaN -> 0
-  return cvt_sat<T>(v);  // saturating v_cvt_u32_f32 + integer min (kmp_wave.h)
-}
-
 // LIN: the LinearPredictor with p = 0 instead of the mean (image/utils.py:58-86 on its 5
 // per-cell channels): pred[cell, k] = fma chain over the 4 nodes (n = dy*2 + dx) from b[k], cast
 // to T; LR = ch0 (x) + ch1 (x-1), UD = ch2 (y) + ch3 (y-1), C = ch4, with the same counts / shifts.
@@ -59,11 +54,7 @@ __device__ __forceinline__ void wave2d_body(const W2& a, int vblk) {
   const int tx = lane & (a.txn - 1);          // txn: a power of two (host)
   const int r = lane >> __builtin_ctz(a.txn);
   const int X = tx * VX;
-  int blk = vblk;
-  if (a.xcd_per > 0) {
-    const int x = blk % 8, k = blk / 8;
-    blk = ((k / a.xcd_per) * 8 + x) * a.xcd_per + (k % a.xcd_per);
-  }
+  const int blk = xcd_block(vblk, a.xcd_per);
   const int grp = blk % a.ngrp;
   const int64_t b = blk / a.ngrp;
   const int Y0 = (grp * a.nwv + wv_) * a.rows;
@@ -171,7 +162,7 @@ __device__ __forceinline__ void wave2d_body(const W2& a, int vblk) {
         acc = __builtin_fmaf(r0[i + 1], w1, acc);
         acc = __builtin_fmaf(r1[i], w2, acc);
         acc = __builtin_fmaf(r1[i + 1], w3, acc);
-        o[i + 1] = cast_t<T>(acc);
+        o[i + 1] = cvt_sat<T>(acc);
       }
     };
     uint32_t P3[VX + 1], U3[VX + 1];
@@ -385,18 +376,12 @@ template <typename T>
 static bool wave2d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, const kmp_region* region,
                             w2::W2& a, dim3& grid, dim3& block) {
   constexpr int VX = 8 / (int)sizeof(T);
-  if (!(std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value)) return false;
   if (opt(OPT_DISABLE_WAVE, 0) || opt(OPT_DISABLE_FAST, 0)) return false;
   if (C != 1 || pred->padding != 0) return false;
   if (pred->kind != KMP_PRED_MEAN && !(pred->kind == KMP_PRED_LINEAR && pred->weights && pred->bias)) return false;
   if (pred->kind == KMP_PRED_LINEAR && opt(OPT_DISABLE_LINEAR_FUSED, 0)) return false;
-  int64_t yb = 0, ye = g.E[1];
-  if (region) {  // only row ranges (full width): the fused chunked drivers' merged slabs
-    if (region->begin[2] > 0 || region->end[2] < g.E[2]) return false;
-    yb = region->begin[1] < 0 ? 0 : region->begin[1];
-    ye = region->end[1] > g.E[1] ? g.E[1] : region->end[1];
-    if (ye <= yb) return false;
-  }
+  int64_t yb, ye;  // only row ranges (full width): the fused chunked drivers' merged slabs
+  if (!region_span(region, g, 1, yb, ye)) return false;
   if (g.n[2] % 2 != 0 || (g.n[2] * (int64_t)sizeof(T)) % 16 != 0) return false;
   if (g.n[1] * g.n[2] >= ((int64_t)1 << 31)) return false;  // 32-bit offsets inside an image
   const int64_t txn = g.E[2] / VX;
@@ -406,12 +391,9 @@ static bool wave2d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predic
   const int64_t waves = ceil_div(g.E[1], rows);
   const int64_t nwv = waves < 4 ? waves : 4;
   const int64_t ngrp = ceil_div(waves, nwv);
-  a.H = (int)g.n[1]; a.W = (int)g.n[2];
-  a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
-  a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  set_extents<2>(a, g);
   a.txn = (int)txn; a.rows = (int)rows; a.nwv = (int)nwv; a.ngrp = (int)ngrp;
-  a.xcd_per = (opt(OPT_W2_XCD, 1) && B % 8 == 0) ? (int)ngrp : 0;
+  a.xcd_per = xcd_per_tile(OPT_W2_XCD, B, ngrp);
   a.ngrp_div = make_udiv((uint32_t)ngrp);
   a.ybeg = (int)yb;
   a.yend = (int)ye;
@@ -447,57 +429,19 @@ static void launch_wave2d(bool one, bool lin, dim3 grid, dim3 block, hipStream_t
   else launch_wave2d_s<T, DEC, false>(one, lin, grid, block, s, a);
 }
 
-template <typename T>
-int try_wave2d_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                      const MapPtrs& maps, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    w2::W2 a{};
-    dim3 grid, block;
-    if (!wave2d_geometry<T>(g, B, C, pred, region, a, grid, block)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 3; ++k)
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    a.wt = pred->weights;
-    a.bias = pred->bias;
-    launch_wave2d<T, false>(a.rows == 1, pred->kind == KMP_PRED_LINEAR, grid, block, stream, a);
-    return check_launch("wave2d_encode");
-  }
-  return KMP_ERR_UNSUPPORTED;
+template <typename T, bool DEC>
+int try_wave2d(const CodecCall<T, DEC>& c) {
+  w2::W2 a{};
+  dim3 grid, block;
+  if (!wave2d_geometry<T>(c.g, c.B, c.C, c.pred, c.region, a, grid, block)) return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 16, 8, 3)) return KMP_ERR_UNSUPPORTED;
+  bind(a, c);
+  a.wt = c.pred->weights;
+  a.bias = c.pred->bias;
+  launch_wave2d<T, DEC>(a.rows == 1, c.pred->kind == KMP_PRED_LINEAR, grid, block, c.stream, a);
+  return check_launch(DEC ? "wave2d_decode" : "wave2d_encode");
 }
 
-template <typename T>
-int try_wave2d_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                      const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    w2::W2 a{};
-    dim3 grid, block;
-    if (!wave2d_geometry<T>(g, B, C, pred, region, a, grid, block)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 3; ++k) {
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    a.wt = pred->weights;
-    a.bias = pred->bias;
-    launch_wave2d<T, true>(a.rows == 1, pred->kind == KMP_PRED_LINEAR, grid, block, stream, a);
-    return check_launch("wave2d_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_W2_INST(T)                                                                                    \
-  template int try_wave2d_encode<T>(const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,     \
-                                    const MapPtrs&, const kmp_region*, hipStream_t);                      \
-  template int try_wave2d_decode<T>(const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,              \
-                                    const kmp_predictor*, T*, const kmp_region*, hipStream_t);
-KMP_W2_INST(uint8_t)
-KMP_W2_INST(uint16_t)
-KMP_W2_INST(int32_t)
-KMP_W2_INST(uint32_t)
+KMP_INST_FAMILY_U8_U16(try_wave2d)
 
 }  // namespace kmp

@@ -31,8 +31,9 @@ struct W2P {
   int32_t txn, rows, nwv, ngrp;
   int32_t xcd_per;
   int32_t ybeg, yend;
-  int32_t wbase;  // first wave (of rows rows) the launch covers
-  int32_t rrun;   // wave2dr_kernel: output rows per wave (a multiple of rows)
+  int32_t pad_;  // unused: keeps rrun's argument offset, on which the kernels' scalar loads and
+                 // registers depend (without it the unrolled kernels take 52 SGPRs instead of 47)
+  int32_t rrun;  // wave2dr_kernel: output rows per wave (a multiple of rows)
 };
 
 // ---- the y-rolling kernel: a wave owns a run of a.rrun consecutive output rows (steps of ``rows``
@@ -62,11 +63,7 @@ __global__ void __launch_bounds__(256) wave2dr_kernel(W2P a) {
   const int tx = lane & (a.txn - 1);
   const int r = lane >> __builtin_ctz(a.txn);
   const int X = tx * VX;
-  int blk = (int)blockIdx.x;
-  if (a.xcd_per > 0) {
-    const int x = blk % 8, k = blk / 8;
-    blk = ((k / a.xcd_per) * 8 + x) * a.xcd_per + (k % a.xcd_per);
-  }
+  const int blk = xcd_block((int)blockIdx.x, a.xcd_per);
   const int grp = blk % a.ngrp;
   const int64_t b = blk / a.ngrp;
   const int rows = a.rows;
@@ -281,41 +278,27 @@ template <typename T>
 static bool wave2dp_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred,
                              const kmp_region* region, int run, w2p::W2P& a, dim3& grid, dim3& block) {
   constexpr int VX = 8 / (int)sizeof(T);
-  if (!(std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value)) return false;
   if (opt(OPT_DISABLE_WAVE, 0) || opt(OPT_DISABLE_FAST, 0)) return false;
   if (C != 1 || pred->kind != KMP_PRED_MEAN || pred->padding < 1 || pred->padding > 2) return false;
   const int P = pred->padding;
-  int64_t yb = 0, ye = g.E[1];
-  if (region) {  // only row ranges (full width)
-    if (region->begin[2] > 0 || region->end[2] < g.E[2]) return false;
-    yb = region->begin[1] < 0 ? 0 : region->begin[1];
-    ye = region->end[1] > g.E[1] ? g.E[1] : region->end[1];
-    if (ye <= yb) return false;
-  }
+  int64_t yb, ye;  // only row ranges (full width)
+  if (!region_span(region, g, 1, yb, ye)) return false;
   if (g.n[2] % 2 != 0 || (g.n[2] * (int64_t)sizeof(T)) % 16 != 0) return false;
   if (g.n[1] * g.n[2] >= ((int64_t)1 << 31)) return false;
   const int64_t txn = g.E[2] / VX;
   if (txn * VX != g.E[2] || txn < 1 || txn > 64 || (txn & (txn - 1)) != 0) return false;
   const int64_t rows = 64 / txn;
   if (rows < P + 1) return false;  // an "above" and a "below" halo row per lane at most
-  // only the waves covering the region's rows are launched
-  int64_t w0 = yb / rows, w1 = ceil_div(ye, rows);
-  // runs of ``run`` rows from the region's first row
+  // only the waves covering the region's rows are launched: runs of ``run`` rows from its first row
   run = (int)(ceil_div(run, rows) * rows);
-  w0 = 0;
-  w1 = ceil_div(ye - yb, (int64_t)run);
-  const int64_t waves = w1 - w0;
+  const int64_t waves = ceil_div(ye - yb, (int64_t)run);
   const int64_t nwv = waves < 4 ? waves : 4;
   const int64_t ngrp = ceil_div(waves, nwv);
-  a.H = (int)g.n[1]; a.W = (int)g.n[2];
-  a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
-  a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  set_extents<2>(a, g);
   a.txn = (int)txn; a.rows = (int)rows; a.nwv = (int)nwv; a.ngrp = (int)ngrp;
-  a.xcd_per = (opt(OPT_W2_XCD, 1) && B % 8 == 0) ? (int)ngrp : 0;
+  a.xcd_per = xcd_per_tile(OPT_W2_XCD, B, ngrp);
   a.ybeg = (int)yb;
   a.yend = (int)ye;
-  a.wbase = (int)w0;
   a.rrun = run;
   const int64_t nblk = B * ngrp;
   grid = dim3((unsigned)nblk);
@@ -343,55 +326,17 @@ static void launch_wave2dp(int P, dim3 grid, dim3 block, hipStream_t s, const w2
   else launch_wave2dp_s<T, DEC, false>(P, grid, block, s, a);
 }
 
-template <typename T>
-int try_wave2dp_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                       const MapPtrs& maps, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    w2p::W2P a{};
-    dim3 grid, block;
-    if (!wave2dp_geometry<T>(g, B, C, pred, region, kW2Run, a, grid, block))
-      return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 3; ++k)
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    launch_wave2dp<T, false>(pred->padding, grid, block, stream, a);
-    return check_launch("wave2dr_encode");
-  }
-  return KMP_ERR_UNSUPPORTED;
+template <typename T, bool DEC>
+int try_wave2dp(const CodecCall<T, DEC>& c) {
+  w2p::W2P a{};
+  dim3 grid, block;
+  if (!wave2dp_geometry<T>(c.g, c.B, c.C, c.pred, c.region, kW2Run, a, grid, block)) return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 16, 8, 3)) return KMP_ERR_UNSUPPORTED;
+  bind(a, c);
+  launch_wave2dp<T, DEC>(c.pred->padding, grid, block, c.stream, a);
+  return check_launch(DEC ? "wave2dr_decode" : "wave2dr_encode");
 }
 
-template <typename T>
-int try_wave2dp_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                       const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    w2p::W2P a{};
-    dim3 grid, block;
-    if (!wave2dp_geometry<T>(g, B, C, pred, region, kW2Run, a, grid, block))
-      return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 3; ++k) {
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    launch_wave2dp<T, true>(pred->padding, grid, block, stream, a);
-    return check_launch("wave2dr_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_W2P_INST(T)                                                                                   \
-  template int try_wave2dp_encode<T>(const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,    \
-                                     const MapPtrs&, const kmp_region*, hipStream_t);                     \
-  template int try_wave2dp_decode<T>(const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,             \
-                                     const kmp_predictor*, T*, const kmp_region*, hipStream_t);
-KMP_W2P_INST(uint8_t)
-KMP_W2P_INST(uint16_t)
-KMP_W2P_INST(int32_t)
-KMP_W2P_INST(uint32_t)
+KMP_INST_FAMILY_U8_U16(try_wave2dp)
 
 }  // namespace kmp

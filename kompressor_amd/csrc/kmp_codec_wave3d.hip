@@ -85,13 +85,7 @@ __device__ __forceinline__ void wave3d_plane_body(const W3& a, int vblk) {
   const int tx = lane & (a.txn - 1);          // txn: a power of two (host)
   const int r = lane >> __builtin_ctz(a.txn);
   const int X = tx * VX;
-  // a.xcd_per > 0: tile-per-XCD order -- XCD x = blockIdx % 8 codes whole tiles, its k-th block
-  // is block (k % per_tile) of tile (k / per_tile) * 8 + x, so the z-halo neighbours share an L2
-  int blk = vblk;
-  if (a.xcd_per > 0) {
-    const int x = blk % 8, k = blk / 8;
-    blk = ((k / a.xcd_per) * 8 + x) * a.xcd_per + (k % a.xcd_per);
-  }
+  int blk = xcd_block(vblk, a.xcd_per);  // tile-per-XCD order: the z-halo neighbours share an L2
   const int yg = blk % a.nyg;
   blk /= a.nyg;
   const int pb = blk % a.nslab;
@@ -384,7 +378,6 @@ template <typename T>
 static bool wave3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, const kmp_region* region,
                             int pl, w3::W3& a, dim3& grid, dim3& block) {
   constexpr int VX = 8 / (int)sizeof(T);
-  if (!(std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value)) return false;
   if (opt(OPT_DISABLE_WAVE, 0) || opt(OPT_DISABLE_FAST, 0)) return false;
   if (C != 1 || pred->kind != KMP_PRED_MEAN || pred->padding != 0) return false;
   if (g.n[2] % 2 != 0 || (g.n[2] * (int64_t)sizeof(T)) % 16 != 0) return false;
@@ -396,17 +389,9 @@ static bool wave3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predic
   const int64_t waves = ceil_div(g.E[1], rows);
   const int64_t nwv = waves < 4 ? waves : 4;
   const int64_t nyg = ceil_div(waves, nwv);
-  int64_t zb = 0, ze = g.E[0];
-  if (region) {
-    if (region->begin[1] > 0 || region->begin[2] > 0 || region->end[1] < g.E[1] || region->end[2] < g.E[2]) return false;
-    zb = region->begin[0] < 0 ? 0 : region->begin[0];
-    ze = region->end[0] > g.E[0] ? g.E[0] : region->end[0];
-    if (ze <= zb) return false;
-  }
-  a.D = (int)g.n[0]; a.H = (int)g.n[1]; a.W = (int)g.n[2];
-  a.Lz = (int)g.L[0]; a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
-  a.Ez = (int)g.E[0]; a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcz = (int)g.Lc[0]; a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  int64_t zb, ze;
+  if (!region_span(region, g, 0, zb, ze)) return false;
+  set_extents<3>(a, g);
   a.txn = (int)txn; a.rows = (int)rows; a.nwv = (int)nwv; a.nyg = (int)nyg;
   const int64_t zext = ze - zb;
   a.zbegin = (int)zb;
@@ -415,7 +400,7 @@ static bool wave3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predic
   a.slab = pl;
   a.nslab = (int)nslab;
   const int64_t nblk = B * nslab * nyg;
-  a.xcd_per = (opt(OPT_W3_XCD, 1) && B % 8 == 0) ? (int)(nslab * nyg) : 0;
+  a.xcd_per = xcd_per_tile(OPT_W3_XCD, B, nslab * nyg);
   a.nt_nodes = 0;
   a.nB = B;
   a.nvblk = (int)nblk;
@@ -445,55 +430,18 @@ static void launch_wave3d(int pl, dim3 grid, dim3 block, hipStream_t stream, con
   else launch_wave3d_s<T, DEC, false>(pl, grid, block, stream, a);
 }
 
-template <typename T>
-int try_wave3d_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                      const MapPtrs& maps, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    w3::W3 a{};
-    dim3 grid, block;
-    const int pl = opt(OPT_W3_PL, 2) == 1 ? 1 : 2;
-    if (!wave3d_geometry<T>(g, B, C, pred, region, pl, a, grid, block)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k)
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    launch_wave3d<T, false>(pl, grid, block, stream, a);
-    return check_launch("wave3d_encode");
-  }
-  return KMP_ERR_UNSUPPORTED;
+template <typename T, bool DEC>
+int try_wave3d(const CodecCall<T, DEC>& c) {
+  w3::W3 a{};
+  dim3 grid, block;
+  const int pl = opt(OPT_W3_PL, 2) == 1 ? 1 : 2;
+  if (!wave3d_geometry<T>(c.g, c.B, c.C, c.pred, c.region, pl, a, grid, block)) return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 16, 8, 7)) return KMP_ERR_UNSUPPORTED;
+  bind(a, c);
+  launch_wave3d<T, DEC>(pl, grid, block, c.stream, a);
+  return check_launch(DEC ? "wave3d_decode" : "wave3d_encode");
 }
 
-template <typename T>
-int try_wave3d_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                      const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    w3::W3 a{};
-    dim3 grid, block;
-    const int pl = opt(OPT_W3_PL, 2) == 1 ? 1 : 2;
-    if (!wave3d_geometry<T>(g, B, C, pred, region, pl, a, grid, block)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k) {
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    launch_wave3d<T, true>(pl, grid, block, stream, a);
-    return check_launch("wave3d_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_W3_INST(T)                                                                                    \
-  template int try_wave3d_encode<T>(const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,     \
-                                    const MapPtrs&, const kmp_region*, hipStream_t);                      \
-  template int try_wave3d_decode<T>(const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,              \
-                                    const kmp_predictor*, T*, const kmp_region*, hipStream_t);
-KMP_W3_INST(uint8_t)
-KMP_W3_INST(uint16_t)
-KMP_W3_INST(int32_t)
-KMP_W3_INST(uint32_t)
+KMP_INST_FAMILY_U8_U16(try_wave3d)
 
 }  // namespace kmp

@@ -78,11 +78,7 @@ __global__ void __launch_bounds__(256) wave3d32_kernel(W32 a) {
   const int tx = lane & (a.txn - 1);
   const int r = lane >> __builtin_ctz(a.txn);
   const int X = tx * VX;
-  int blk = (int)blockIdx.x;
-  if (a.xcd_per > 0) {
-    const int x = blk % 8, k = blk / 8;
-    blk = ((k / a.xcd_per) * 8 + x) * a.xcd_per + (k % a.xcd_per);
-  }
+  int blk = xcd_block((int)blockIdx.x, a.xcd_per);
   const int yg = blk % a.nyg;
   blk /= a.nyg;
   const int pb = blk % a.nslab;
@@ -315,7 +311,6 @@ template <typename T>
 static bool wave3d32_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred,
                               const kmp_region* region, w32::W32& a, dim3& grid, dim3& block) {
   constexpr int VX = 2;
-  if (!(std::is_same<T, uint32_t>::value || std::is_same<T, int32_t>::value)) return false;
   if (opt(OPT_DISABLE_WAVE, 0) || opt(OPT_DISABLE_FAST, 0)) return false;
   if (C != 1 || pred->kind != KMP_PRED_MEAN || pred->padding != 0) return false;
   if (g.n[2] % 2 != 0 || (g.n[2] * (int64_t)sizeof(T)) % 16 != 0) return false;
@@ -327,76 +322,33 @@ static bool wave3d32_geometry(const Geo& g, int64_t B, int64_t C, const kmp_pred
   const int64_t waves = ceil_div(g.E[1], rows);
   const int64_t nwv = waves < 4 ? waves : 4;
   const int64_t nyg = ceil_div(waves, nwv);
-  int64_t zb = 0, ze = g.E[0];
-  if (region) {
-    if (region->begin[1] > 0 || region->begin[2] > 0 || region->end[1] < g.E[1] || region->end[2] < g.E[2]) return false;
-    zb = region->begin[0] < 0 ? 0 : region->begin[0];
-    ze = region->end[0] > g.E[0] ? g.E[0] : region->end[0];
-    if (ze <= zb) return false;
-  }
-  a.D = (int)g.n[0]; a.H = (int)g.n[1]; a.W = (int)g.n[2];
-  a.Lz = (int)g.L[0]; a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
-  a.Ez = (int)g.E[0]; a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcz = (int)g.Lc[0]; a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  int64_t zb, ze;
+  if (!region_span(region, g, 0, zb, ze)) return false;
+  set_extents<3>(a, g);
   a.txn = (int)txn; a.rows = (int)rows; a.nwv = (int)nwv; a.nyg = (int)nyg;
   a.zbegin = (int)zb;
   a.zend = (int)ze;
   const int64_t nslab = ceil_div(ze - zb, (int64_t)kW32PL);
   a.nslab = (int)nslab;
   const int64_t nblk = B * nslab * nyg;
-  a.xcd_per = (opt(OPT_W3_XCD, 1) && B % 8 == 0) ? (int)(nslab * nyg) : 0;
+  a.xcd_per = xcd_per_tile(OPT_W3_XCD, B, nslab * nyg);
   grid = dim3((unsigned)nblk);
   block = dim3((unsigned)(64 * nwv));
   return nblk < ((int64_t)1 << 31);
 }
 
-template <typename T>
-int try_wave3d32_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                        const MapPtrs& maps, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint32_t>::value || std::is_same<T, int32_t>::value) {
-    w32::W32 a{};
-    dim3 grid, block;
-    if (!wave3d32_geometry<T>(g, B, C, pred, region, a, grid, block)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k)
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    w32::wave3d32_kernel<T, false, kW32PL><<<grid, block, 0, stream>>>(a);
-    return check_launch("wave3d32_encode");
-  }
-  return KMP_ERR_UNSUPPORTED;
+template <typename T, bool DEC>
+int try_wave3d32(const CodecCall<T, DEC>& c) {
+  w32::W32 a{};
+  dim3 grid, block;
+  if (!wave3d32_geometry<T>(c.g, c.B, c.C, c.pred, c.region, a, grid, block)) return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 16, 8, 7)) return KMP_ERR_UNSUPPORTED;
+  bind(a, c);
+  w32::wave3d32_kernel<T, DEC, kW32PL><<<grid, block, 0, c.stream>>>(a);
+  return check_launch(DEC ? "wave3d32_decode" : "wave3d32_encode");
 }
 
-template <typename T>
-int try_wave3d32_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                        const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint32_t>::value || std::is_same<T, int32_t>::value) {
-    w32::W32 a{};
-    dim3 grid, block;
-    if (!wave3d32_geometry<T>(g, B, C, pred, region, a, grid, block)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k) {
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    w32::wave3d32_kernel<T, true, kW32PL><<<grid, block, 0, stream>>>(a);
-    return check_launch("wave3d32_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_W32_INST(T)                                                                                   \
-  template int try_wave3d32_encode<T>(const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,   \
-                                      const MapPtrs&, const kmp_region*, hipStream_t);                    \
-  template int try_wave3d32_decode<T>(const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,            \
-                                      const kmp_predictor*, T*, const kmp_region*, hipStream_t);
-KMP_W32_INST(uint8_t)
-KMP_W32_INST(uint16_t)
-KMP_W32_INST(int32_t)
-KMP_W32_INST(uint32_t)
+KMP_INST_FAMILY(try_wave3d32, int32_t)
+KMP_INST_FAMILY(try_wave3d32, uint32_t)
 
 }  // namespace kmp

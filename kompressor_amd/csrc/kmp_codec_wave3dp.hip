@@ -73,11 +73,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   const int tx = lane & (a.txn - 1);
   const int r = lane >> __builtin_ctz(a.txn);
   const int X = tx * VX;
-  int blk = (int)blockIdx.x;
-  if (a.xcd_per > 0) {
-    const int x = blk % 8, k = blk / 8;
-    blk = ((k / a.xcd_per) * 8 + x) * a.xcd_per + (k % a.xcd_per);
-  }
+  int blk = xcd_block((int)blockIdx.x, a.xcd_per);
   const int yg = blk % a.nyg;
   blk /= a.nyg;
   const int pb = blk % a.nslab;
@@ -352,11 +348,7 @@ wave3dr_kernel(W3P a) {
   const int tx = lane & (a.txn - 1);
   const int r = lane >> __builtin_ctz(a.txn);
   const int X = tx * VX;
-  int blk = (int)blockIdx.x;
-  if (a.xcd_per > 0) {
-    const int x = blk % 8, k = blk / 8;
-    blk = ((k / a.xcd_per) * 8 + x) * a.xcd_per + (k % a.xcd_per);
-  }
+  int blk = xcd_block((int)blockIdx.x, a.xcd_per);
   const int yg = blk % a.nyg;
   blk /= a.nyg;
   const int pb = blk % a.nslab;
@@ -650,7 +642,6 @@ template <typename T>
 static bool wave3dp_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred,
                              const kmp_region* region, int pl, w3p::W3P& a, dim3& grid, dim3& block) {
   constexpr int VX = 8 / (int)sizeof(T);
-  if (!(std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value)) return false;
   if (opt(OPT_DISABLE_WAVE, 0) || opt(OPT_DISABLE_FAST, 0)) return false;
   if (C != 1 || pred->kind != KMP_PRED_MEAN || pred->padding < 1 || pred->padding > 2) return false;
   const int P = pred->padding;
@@ -663,24 +654,16 @@ static bool wave3dp_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predi
   const int64_t waves = ceil_div(g.E[1], rows);
   const int64_t nwv = waves < 4 ? waves : 4;
   const int64_t nyg = ceil_div(waves, nwv);
-  int64_t zb = 0, ze = g.E[0];
-  if (region) {
-    if (region->begin[1] > 0 || region->begin[2] > 0 || region->end[1] < g.E[1] || region->end[2] < g.E[2]) return false;
-    zb = region->begin[0] < 0 ? 0 : region->begin[0];
-    ze = region->end[0] > g.E[0] ? g.E[0] : region->end[0];
-    if (ze <= zb) return false;
-  }
-  a.D = (int)g.n[0]; a.H = (int)g.n[1]; a.W = (int)g.n[2];
-  a.Lz = (int)g.L[0]; a.Ly = (int)g.L[1]; a.Lx = (int)g.L[2];
-  a.Ez = (int)g.E[0]; a.Ey = (int)g.E[1]; a.Ex = (int)g.E[2];
-  a.Lcz = (int)g.Lc[0]; a.Lcy = (int)g.Lc[1]; a.Lcx = (int)g.Lc[2];
+  int64_t zb, ze;
+  if (!region_span(region, g, 0, zb, ze)) return false;
+  set_extents<3>(a, g);
   a.txn = (int)txn; a.rows = (int)rows; a.nwv = (int)nwv; a.nyg = (int)nyg;
   a.zbegin = (int)zb;
   a.zend = (int)ze;
   const int64_t nslab = ceil_div(ze - zb, (int64_t)pl);
   a.nslab = (int)nslab;
   const int64_t nblk = B * nslab * nyg;
-  a.xcd_per = (opt(OPT_W3_XCD, 1) && B % 8 == 0) ? (int)(nslab * nyg) : 0;
+  a.xcd_per = xcd_per_tile(OPT_W3_XCD, B, nslab * nyg);
   grid = dim3((unsigned)nblk);
   block = dim3((unsigned)(64 * nwv));
   return nblk < ((int64_t)1 << 31);
@@ -736,69 +719,27 @@ static void launch_wave3dp(int P, int pl, int wpe, dim3 grid, dim3 block, hipStr
   else launch_wave3dp_s<T, DEC, false>(P, pl, wpe, grid, block, stream, a);
 }
 
-template <typename T>
-int try_wave3dp_encode(const T* hi, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, T* lowres,
-                       const MapPtrs& maps, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    w3p::W3P a{};
-    dim3 grid, block;
-    int pl, wpe;
-    w3p_cfg(pred->padding, false, (int)sizeof(T), pl, wpe);
-    const int zr = w3p_roll(pred->padding, (int)sizeof(T));
-    if (!wave3dp_geometry<T>(g, B, C, pred, region, zr ? zr : pl, a, grid, block)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k)
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-    a.hi_in = hi;
-    a.lo_out = lowres;
-    a.maps = maps;
-    if (zr) {
-      a.zrun = zr;
-      launch_wave3dr<T, false>(pred->padding, grid, block, stream, a);
-      return check_launch("wave3dr_encode");
-    }
-    launch_wave3dp<T, false>(pred->padding, pl, wpe, grid, block, stream, a);
-    return check_launch("wave3dp_encode");
+template <typename T, bool DEC>
+int try_wave3dp(const CodecCall<T, DEC>& c) {
+  const int P = c.pred->padding;
+  w3p::W3P a{};
+  dim3 grid, block;
+  int pl, wpe;
+  w3p_cfg(P, DEC, (int)sizeof(T), pl, wpe);
+  const int zr = w3p_roll(P, (int)sizeof(T));
+  if (!wave3dp_geometry<T>(c.g, c.B, c.C, c.pred, c.region, zr ? zr : pl, a, grid, block))
+    return KMP_ERR_UNSUPPORTED;
+  if (!ptrs_aligned(c, 16, 8, 7)) return KMP_ERR_UNSUPPORTED;
+  bind(a, c);
+  if (zr) {
+    a.zrun = zr;
+    launch_wave3dr<T, DEC>(P, grid, block, c.stream, a);
+    return check_launch(DEC ? "wave3dr_decode" : "wave3dr_encode");
   }
-  return KMP_ERR_UNSUPPORTED;
+  launch_wave3dp<T, DEC>(P, pl, wpe, grid, block, c.stream, a);
+  return check_launch(DEC ? "wave3dp_decode" : "wave3dp_encode");
 }
 
-template <typename T>
-int try_wave3dp_decode(const T* lowres, const CMapPtrs& maps, const Geo& g, int64_t B, int64_t C,
-                       const kmp_predictor* pred, T* hi, const kmp_region* region, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint16_t>::value || std::is_same<T, uint8_t>::value) {
-    w3p::W3P a{};
-    dim3 grid, block;
-    int pl, wpe;
-    w3p_cfg(pred->padding, true, (int)sizeof(T), pl, wpe);
-    const int zr = w3p_roll(pred->padding, (int)sizeof(T));
-    if (!wave3dp_geometry<T>(g, B, C, pred, region, zr ? zr : pl, a, grid, block)) return KMP_ERR_UNSUPPORTED;
-    if (((uintptr_t)hi & 15) || ((uintptr_t)lowres & 7)) return KMP_ERR_UNSUPPORTED;
-    for (int k = 0; k < 7; ++k) {
-      if ((uintptr_t)maps.p[k] & 7) return KMP_ERR_UNSUPPORTED;
-      a.maps.p[k] = (void*)maps.p[k];
-    }
-    a.hi_out = hi;
-    a.lo_in = lowres;
-    if (zr) {
-      a.zrun = zr;
-      launch_wave3dr<T, true>(pred->padding, grid, block, stream, a);
-      return check_launch("wave3dr_decode");
-    }
-    launch_wave3dp<T, true>(pred->padding, pl, wpe, grid, block, stream, a);
-    return check_launch("wave3dp_decode");
-  }
-  return KMP_ERR_UNSUPPORTED;
-}
-
-#define KMP_W3P_INST(T)                                                                                   \
-  template int try_wave3dp_encode<T>(const T*, const Geo&, int64_t, int64_t, const kmp_predictor*, T*,    \
-                                     const MapPtrs&, const kmp_region*, hipStream_t);                     \
-  template int try_wave3dp_decode<T>(const T*, const CMapPtrs&, const Geo&, int64_t, int64_t,             \
-                                     const kmp_predictor*, T*, const kmp_region*, hipStream_t);
-KMP_W3P_INST(uint8_t)
-KMP_W3P_INST(uint16_t)
-KMP_W3P_INST(int32_t)
-KMP_W3P_INST(uint32_t)
+KMP_INST_FAMILY_U8_U16(try_wave3dp)
 
 }  // namespace kmp

@@ -7,7 +7,7 @@
 // grid-stride loops, 256-thread workgroups.  The fused one-pass codec lives in kmp_codec*.hip.
 #include <mutex>
 
-#include "kmp_aggregate.h"
+#include "kmp_wave.h"
 
 namespace kmp {
 
@@ -688,11 +688,8 @@ __global__ void __launch_bounds__(kThreads) mean_predict_plane_kernel(
   constexpr float NN = (float)(KK * KK * KK);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int32_t nplanes = Lcz + 1, ngrp = (nplanes + PPB - 1) / PPB;
-  int32_t blk = (int32_t)blockIdx.x;
-  if (xcd_per > 0) {  // consecutive planes of one window on one XCD: shared node planes hit its L2
-    const int32_t x = blk % 8, k = blk / 8;
-    blk = ((k / xcd_per) * 8 + x) * xcd_per + (k % xcd_per);
-  }
+  // consecutive planes of one window on one XCD: shared node planes hit its L2
+  int32_t blk = wv::xcd_block((int32_t)blockIdx.x, xcd_per);
   const int32_t oz = (blk % ngrp) * PPB;  // the first output plane; cell slot s is plane oz - 1 + s
   const int64_t b = blk / ngrp;
   const int32_t S1 = S.e[1], S2 = S.e[2], plane = S1 * S2;
@@ -830,11 +827,8 @@ __global__ void __launch_bounds__(kThreads) mean_predict_p0x8_kernel(const T* __
                                                                     int32_t Lcz, int32_t Lcy, int32_t Lcx, MapPtrs outs,
                                                                     int32_t xcd_per, int32_t ZP, int32_t ngrp) {
   extern __shared__ __attribute__((aligned(16))) uint32_t cl[];  // [ZP + 1][Lcy + 2][Lcx + 8]
-  int32_t blk = (int32_t)blockIdx.x;
-  if (xcd_per > 0) {  // the groups of one window on one XCD (their shared node planes hit its L2)
-    const int32_t x = blk % 8, k = blk / 8;
-    blk = ((k / xcd_per) * 8 + x) * xcd_per + (k % xcd_per);
-  }
+  // the groups of one window on one XCD (their shared node planes hit its L2)
+  int32_t blk = wv::xcd_block((int32_t)blockIdx.x, xcd_per);
   const int32_t b = blk / ngrp, z0 = (blk - b * ngrp) * ZP;  // output planes z0 .. z0 + ZP - 1
   const int32_t RP = Lcx + 8, PW = mp8_plane_words(Lcy, Lcx), NJ = Lcx >> 3;
   const int32_t S1 = S.e[1], S2 = S.e[2];

@@ -1,6 +1,6 @@
-// kmp_wave.h -- register-level helpers shared by the barrier-free wave kernels
-// (kmp_codec_wave3d.hip, kmp_codec_wave2d.hip): streaming vector loads / stores, element
-// (un)packing of 8- and 16-byte row segments, the padded-node index map, and cross-lane shuffles.
+// kmp_wave.h -- register-level helpers shared by the one-pass codec kernels (kmp_codec_*.hip):
+// streaming vector loads / stores, element (un)packing of 8- and 16-byte row segments, the
+// padded-node index maps, the XCD block order, and cross-lane shuffles.
 #pragma once
 
 #include "kmp_codec.h"
@@ -156,6 +156,29 @@ __device__ __forceinline__ int lsrc1(int r, int L, int E) {
   int m = r < 0 ? -1 - r : r;
   m = m >= L ? 2 * L - 1 - m : m;
   return m >= E ? 2 * E - 1 - m : m;
+}
+
+// lsrc by remainders (neighbourhood symmetric pad, then even reflect pad), as the LDS kernels
+// (kmp_codec_fast3d.hip, kmp_codec_fast2d.hip) were measured with: not interchangeable with lsrc,
+// whose form exists to keep these divisions out of the wave kernels
+__device__ __forceinline__ int lsrc_mod(int r, int L, int E) {
+  int m = r % (2 * L);
+  if (m < 0) m += 2 * L;
+  m = m < L ? m : 2 * L - 1 - m;
+  int m2 = m % (2 * E);
+  m2 = m2 < E ? m2 : 2 * E - 1 - m2;
+  return m2;
+}
+
+// xcd_per > 0: tile-per-XCD block order -- XCD x = blk % 8 codes whole tiles of xcd_per blocks, its
+// k-th block is block (k % xcd_per) of tile (k / xcd_per) * 8 + x, so the blocks that share halo
+// rows / planes share an L2; xcd_per == 0: the identity
+__device__ __forceinline__ int xcd_block(int blk, int xcd_per) {
+  if (xcd_per > 0) {
+    const int x = blk % 8, k = blk / 8;
+    blk = ((k / xcd_per) * 8 + x) * xcd_per + (k % xcd_per);
+  }
+  return blk;
 }
 
 // astype(uint8 / uint16) of an f32 (XLA: truncate toward zero, saturate, NaN -> 0):
