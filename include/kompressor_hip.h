@@ -341,6 +341,38 @@ int kmp_rice_bundle_decode(int32_t dtype, const kmp_rice_array* arrays, int32_t 
                            const uint8_t* bundle, int64_t payload_off, uint64_t payload_words,
                            unsigned long long* bad, kmp_stream_t stream);
 
+/* Decode of SAMPLE RANGES of bundle arrays (extends kmp_rice_bundle_decode, which always decodes  */
+/* whole arrays from a whole resident bundle; no reference counterpart, as above).  One record   */
+/* decodes samples [first, end) of one array; its tiles T0 = first / 16384 .. T1 = (end - 1) /    */
+/* 16384 are the only ones read.  The side information, the tile table and the payload are       */
+/* separate device pointers, so each may point into a resident bundle or at a small WINDOW of a   */
+/* bundle that is mostly not on the device (a partial file read):                                */
+typedef struct kmp_rice_range {
+  void* samples;           /* out: samples[i - first] = sample i of the array, first <= i < end;  */
+                           /* no other byte is written                                             */
+  int64_t n;               /* samples of the whole array (fixes the block count, the short last   */
+                           /* block)                                                               */
+  int64_t first, end;      /* 0 <= first < end <= n                                                */
+  const uint8_t* params;   /* params / bw from block 256 * T0 on, up to block                     */
+  const uint8_t* bw;       /* min(ceil(n / 64), 256 * (T1 + 1)) - 1                               */
+  const uint64_t* toff;    /* 8-aligned: the word offsets of tiles T0 .. T1, then ONE closing     */
+                           /* entry (the next tile's offset, or the array's end word after its   */
+                           /* last tile): T1 - T0 + 2 entries                                      */
+  const uint32_t* payload; /* 4-aligned: the payload from word ``payload_first`` on               */
+  uint64_t payload_first;  /* the payload word payload[0] holds: 0 for a bundle's whole payload   */
+                           /* region, toff[0] for a window cut at the first touched tile          */
+  uint64_t payload_words;  /* words readable at ``payload``                                        */
+} kmp_rice_range;
+/* One launch for ``count`` (<= 32) records of one dtype; the grid is one workgroup per touched   */
+/* tile.  Per touched tile the checks of kmp_rice_bundle_decode (k < W, bw within [2k + 2, 2W + 2], */
+/* a zero block without payload, the tile's words meeting the closing offset, every read inside  */
+/* [payload_first, payload_first + payload_words)); a tile that fails decodes as zeros and adds 1 */
+/* to *bad (caller-zeroed device uint64).  That an array's first tile starts at its record's     */
+/* first word is the caller's check (the record is not passed).  No allocation, no             */
+/* synchronisation; graph-capturable.                                                            */
+int kmp_rice_bundle_decode_ranges(int32_t dtype, const kmp_rice_range* ranges, int32_t count,
+                                  unsigned long long* bad, kmp_stream_t stream);
+
 /* CRC-32 (zlib / IEEE: reflected 0xEDB88320, init and final xor 0xFFFFFFFF; == zlib.crc32) of   */
 /* ``data`` into the device uint32 *crc_out (kmp_crc.hip): the container file's integrity check    */
 /* (container.py; the reference has no file format, volume/encode_decode.py:56   */

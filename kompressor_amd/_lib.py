@@ -53,6 +53,13 @@ class RiceArray(ctypes.Structure):  # kmp_rice_array (include/kompressor_hip.h)
                 ('toff_off', ctypes.c_int64), ('rec_off', ctypes.c_int64)]
 
 
+class RiceRange(ctypes.Structure):  # kmp_rice_range (include/kompressor_hip.h)
+    _fields_ = [('samples', ctypes.c_void_p), ('n', ctypes.c_int64), ('first', ctypes.c_int64),
+                ('end', ctypes.c_int64), ('params', ctypes.c_void_p), ('bw', ctypes.c_void_p),
+                ('toff', ctypes.c_void_p), ('payload', ctypes.c_void_p), ('payload_first', ctypes.c_uint64),
+                ('payload_words', ctypes.c_uint64)]
+
+
 class Region(ctypes.Structure):
     _fields_ = [('begin', ctypes.c_int64 * 3), ('end', ctypes.c_int64 * 3)]
 
@@ -113,6 +120,7 @@ _PROTOS = {
     'kmp_rice_bundle_workspace_bytes': (ctypes.c_int64, [_i64]),
     'kmp_rice_bundle_encode': (ctypes.c_int, [_i32, _vp, _i32, _i64, _i64, _vp, _i64, _vp, _vp]),
     'kmp_rice_bundle_decode': (ctypes.c_int, [_i32, _vp, _i32, _i64, _vp, _i64, ctypes.c_uint64, _vp, _vp]),
+    'kmp_rice_bundle_decode_ranges': (ctypes.c_int, [_i32, _vp, _i32, _vp, _vp]),
     'kmp_crc32': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp]),
     'kmp_decode_with_predictions': (ctypes.c_int, [_i32, _i32, _i32, _vp, _vpp, _i64, _i64p, _i64, _i32p, _vpp,
                                                    _vp, _vp]),

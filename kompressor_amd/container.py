@@ -184,31 +184,38 @@ def save(path, lowres, encoded, predictor=None, padding=None, ndim=None, method=
     return _write(path, meta, blob, total, crc, t0)
 
 
+def _read_head(f, path):
+    """``(version, meta, metadata bytes, bundle bytes)`` of the open file ``f``: the header and the
+    metadata JSON, checked, with the bundle's recorded length checked against the file's size."""
+    head = f.read(_HEAD.size)
+    if len(head) < _HEAD.size:
+        raise ValueError(f'{path}: not a kompressor_amd file (too short)')
+    magic, version, _, mlen = _HEAD.unpack(head)
+    if magic != MAGIC or version not in (1, 2, VERSION) or mlen > (1 << 26):
+        raise ValueError(f'{path}: not a kompressor_amd file (magic {magic!r}, version {version})')
+    try:
+        meta = json.loads(f.read(mlen).decode())
+        n = int(meta['bundle_bytes'])
+    except (ValueError, KeyError, TypeError) as e:
+        raise ValueError(f'{path}: corrupt metadata ({e})') from None
+    if version == 1 and meta.get('method') != 'planes':
+        # version-1 'rice' payloads were the per-array KMPR format, replaced by the v2 bundle;
+        # version-1 'planes' payloads are unchanged and still read
+        raise ValueError(f'{path}: a version-1 rice file (the retired per-array KMPR format): re-compress it')
+    # the payload length is checked against the file before anything is allocated for it
+    avail = os.fstat(f.fileno()).st_size - (_HEAD.size + mlen)
+    if not 0 <= n <= avail:
+        raise ValueError(f'{path}: truncated or corrupt ({n} payload bytes recorded, {max(avail, 0)} present)')
+    return version, meta, mlen, n
+
+
 def _read(path):
     """``(meta, device bundle, device crc, timing)``: the file's bundle read straight into the pinned
     staging buffer, uploaded, and its CRC-32 launched on the device (checked by the caller together
     with the decode's own synchronisation -- ``_check_crc``)."""
     t0 = time.perf_counter()
     with open(path, 'rb') as f:
-        head = f.read(_HEAD.size)
-        if len(head) < _HEAD.size:
-            raise ValueError(f'{path}: not a kompressor_amd file (too short)')
-        magic, version, _, mlen = _HEAD.unpack(head)
-        if magic != MAGIC or version not in (1, 2, VERSION) or mlen > (1 << 26):
-            raise ValueError(f'{path}: not a kompressor_amd file (magic {magic!r}, version {version})')
-        try:
-            meta = json.loads(f.read(mlen).decode())
-            n = int(meta['bundle_bytes'])
-        except (ValueError, KeyError, TypeError) as e:
-            raise ValueError(f'{path}: corrupt metadata ({e})') from None
-        if version == 1 and meta.get('method') != 'planes':
-            # version-1 'rice' payloads were the per-array KMPR format, replaced by the v2 bundle;
-            # version-1 'planes' payloads are unchanged and still read
-            raise ValueError(f'{path}: a version-1 rice file (the retired per-array KMPR format): re-compress it')
-        # the payload length is checked against the file before anything is allocated for it
-        avail = os.fstat(f.fileno()).st_size - (_HEAD.size + mlen)
-        if not 0 <= n <= avail:
-            raise ValueError(f'{path}: truncated or corrupt ({n} payload bytes recorded, {max(avail, 0)} present)')
+        version, meta, mlen, n = _read_head(f, path)
         # the payload: parallel page-cache reads into pinned chunks, each uploaded while the next is read
         blob = torch.empty((max(n, 1),), dtype=torch.uint8, device='cuda')[:n]
         fd, base = f.fileno(), _HEAD.size + mlen
@@ -288,19 +295,15 @@ def compress(path, highres, predictor, levels='auto', method='rice'):
             'levels': levels}
 
 
-def decompress(path, predictor=None, as_numpy=True):
-    """Decode a file written by :func:`compress` (or :func:`save`) back to the original array, bit
-    for bit, coarsest level first.  A file coded with an external predictions_fn needs it passed."""
-    t0 = time.perf_counter()
-    meta, blob, crc, tm = _read(path)
-    _check_crc(path, meta, crc)
-    t1 = time.perf_counter()
-    lowres, (arrays, bundle_dims) = packing.unpack_encoded(blob)
+def _decode_predictor(path, meta, predictor, dtype):
+    """The predictor a file decodes with -- the one passed, or the file's own -- checked against the
+    file's padding and a LinearPredictor's arithmetic (``dtype``: the coded samples' torch dtype).
+    Shared by :func:`decompress` and :func:`read_region`."""
     pred = predictor or predictor_from_meta(meta)
     if pred is None:
         raise AssertionError(f'{path} was coded with an external predictions_fn '
                              f'({meta["predictor"]["name"] if meta["predictor"] else "unknown"}): pass it')
-    ndim, padding = meta['ndim'], meta['padding']
+    padding = meta['padding']
     if isinstance(pred, (MeanPredictor, LinearPredictor)) and pred.padding != padding:
         raise AssertionError(f'{path} was coded with padding {padding}; the predictor passed has {pred.padding}')
     if isinstance(pred, LinearPredictor) and meta['predictor'] and meta['predictor'].get('kind') == 'linear':
@@ -309,9 +312,22 @@ def decompress(path, predictor=None, as_numpy=True):
         arith = meta['predictor'].get('arith', 'f32')
         if pred.arith == 'auto':  # a default-constructed predictor takes the file's arithmetic
             pred = LinearPredictor(pred.weights, pred.bias, pred.padding, pred.ndim, arith=arith)
-        if pred.arith_for(lowres.dtype) != arith:
+        if pred.arith_for(dtype) != arith:
             raise AssertionError(f"{path} was coded with arith='{arith}'; the predictor passed evaluates with "
-                                 f"arith='{pred.arith_for(lowres.dtype)}'")
+                                 f"arith='{pred.arith_for(dtype)}'")
+    return pred
+
+
+def decompress(path, predictor=None, as_numpy=True):
+    """Decode a file written by :func:`compress` (or :func:`save`) back to the original array, bit
+    for bit, coarsest level first.  A file coded with an external predictions_fn needs it passed."""
+    t0 = time.perf_counter()
+    meta, blob, crc, tm = _read(path)
+    _check_crc(path, meta, crc)
+    t1 = time.perf_counter()
+    lowres, (arrays, bundle_dims) = packing.unpack_encoded(blob)
+    pred = _decode_predictor(path, meta, predictor, lowres.dtype)
+    ndim, padding = meta['ndim'], meta['padding']
     nmaps = _nd.NMAPS[ndim]
     levels = meta.get('levels') or [{'dims': list(bundle_dims)}]  # save(): one level, dims in the bundle
     if len(arrays) != nmaps * len(levels):
@@ -345,3 +361,312 @@ def _coder_fn(coder, ndim):
     from . import utils
     name = {0: 'decode_values_raw', 1: 'decode_values_uint8', 2: 'decode_values_uint16', 3: 'decode_values_uint32'}
     return getattr(utils, name[coder])
+
+
+# ---------------------------------------------------------------------------------------------
+# partial reads: only the planes / batch items asked for are read, uploaded and decoded
+#
+# A v2 Rice bundle is tile-addressable (per array a table of u64 word offsets, one per tile of
+# 16384 samples, plus per-block side information) and the codec is plane-addressable (output
+# planes [z0, z1) of a level need lowres planes slabs.decode_halo(E, z0, z1, p) and that range's
+# map planes only).  ``plan_region`` composes the two down the pyramid; ``read_region`` preads
+# the table, side-information and payload windows of the touched tiles, decodes them with
+# kmp_rice_bundle_decode_ranges into local arrays and runs the fused decode's z-region level by
+# level, coarsest first.
+# ---------------------------------------------------------------------------------------------
+
+_TILE = 16384  # samples per tile of a v2 Rice bundle (256 blocks of 64)
+
+
+def info(path):
+    """What a file holds, from its header and metadata alone (no payload read, no GPU):
+    ``{'shape', 'sample_dtype', 'ndim', 'levels', 'padding', 'predictor', 'method', 'version',
+    'file_bytes', 'bundle_bytes'}`` -- ``shape`` is the array :func:`decompress` returns, the one a
+    :func:`read_region` selection indexes."""
+    with open(path, 'rb') as f:
+        version, meta, mlen, n = _read_head(f, path)
+        size = os.fstat(f.fileno()).st_size
+    try:
+        shapes = _meta_shapes(meta)
+        pred = meta.get('predictor') or {}
+        return {'shape': tuple(shapes[0][0]), 'sample_dtype': meta.get('sample_dtype') or meta.get('lowres_dtype'),
+                'ndim': int(meta['ndim']), 'levels': len(shapes), 'padding': int(meta['padding']),
+                'predictor': pred.get('kind'), 'method': meta.get('method'), 'version': version,
+                'file_bytes': int(size), 'bundle_bytes': int(n)}
+    except (KeyError, TypeError, IndexError) as e:
+        raise ValueError(f'{path}: corrupt metadata ({e!r})') from None
+
+
+def _meta_shapes(meta):
+    """Per pyramid level, finest first: ``(highres shape, lowres shape, map shapes, dims)`` from the
+    metadata alone (a :func:`save` file: one level, the highres shape from the lowres's and dims)."""
+    ndim = int(meta['ndim'])
+    if meta.get('levels'):
+        hs = [tuple(int(s) for s in lv['highres_shape']) for lv in meta['levels']]
+    else:
+        lo, dims = [int(s) for s in meta['lowres_shape']], [int(d) for d in meta['dims']]
+        hs = [(lo[0], *[2 * e - 1 + d for e, d in zip(lo[1:1 + ndim], dims)], *lo[1 + ndim:])]
+    out = []
+    for h in hs:
+        if len(h) < 1 + ndim or any(s < 1 for s in h):
+            raise ValueError(f'bad level shape {h} in the metadata')
+        lo, maps, dims = _nd.encoded_shapes(h, ndim)
+        out.append((tuple(h), tuple(int(s) for s in lo), [tuple(int(s) for s in m) for m in maps], tuple(dims)))
+    for (_, lo, _, _), (h, _, _, _) in zip(out, out[1:]):
+        if lo != h:
+            raise ValueError(f'level shapes in the metadata do not nest ({lo} then {h})')
+    if out[-1][1] != tuple(int(s) for s in meta['lowres_shape']):
+        raise ValueError('the coarsest lowres shape in the metadata does not match its levels')
+    return out
+
+
+def _clamp_range(r, extent, what):
+    if r is None:
+        return 0, int(extent)
+    lo, hi = max(int(r[0]), 0), min(int(r[1]), int(extent))
+    if hi <= lo:
+        raise ValueError(f'{what}={tuple(r)} selects nothing of {extent}')
+    return lo, hi
+
+
+def _tiles(n):
+    return -(-(-(-n // 64)) // 256) if n > 0 else 0
+
+
+def plan_region(meta, planes=None, batch=None):
+    """The arrays a selection needs, as a pure function of the file's metadata.  ``planes = (z0, z1)``
+    selects highres planes along the first spatial axis (volumes only), ``batch = (b0, b1)`` items of
+    the leading axis; both are clamped to the array, an empty or reversed range raises ValueError.
+
+    From the finest level down, highres planes ``[a, b)`` of a level are its output planes
+    ``(a // 2, (b + 1) // 2)``, which need the lowres planes ``slabs.decode_halo`` of them -- the next
+    level's highres planes -- and each map's planes ``[z0, min(z1, the map's z extent))``.  Returns
+    ``{'batch', 'planes', 'levels': [{'highres', 'out', 'lowres', 'maps', 'at_top', 'dims'}] finest
+    first, 'lowres': the coarsest lowres planes, 'arrays': one entry per bundle array in bundle order
+    (the coarsest lowres, then every level's maps, finest first) with its full ``shape``, the selected
+    planes ``sel``, the ``local_shape`` it is decoded into, the plane ``local_at`` the selection starts
+    at there and ``ranges`` [(first sample, end sample, destination sample)], 'tiles_decoded',
+    'tiles_total'}``."""
+    ndim, p = int(meta['ndim']), int(meta['padding'])
+    shapes = _meta_shapes(meta)
+    full = shapes[0][0]
+    if planes is not None and ndim != 3:
+        raise ValueError('planes selects along the first spatial axis of a volume; an image file takes batch only')
+    b0, b1 = _clamp_range(batch, full[0], 'batch')
+    a, b = _clamp_range(planes, full[1], 'planes')
+    bsel = b1 - b0
+
+    def entry(shape, sel, local_z, local_at):
+        per = dev.prod(shape[2:])
+        z = shape[1]
+        s0, s1 = sel
+        local_shape = (bsel, local_z, *shape[2:])
+        if s1 <= s0:
+            ranges = []
+        elif (s0, s1) == (0, z) and local_z == z:
+            ranges = [(b0 * z * per, b1 * z * per, 0)]
+        else:
+            ranges = [((bi * z + s0) * per, (bi * z + s1) * per, ((bi - b0) * local_z + local_at) * per)
+                      for bi in range(b0, b1)]
+        return {'shape': tuple(shape), 'sel': (s0, max(s0, s1)), 'local_shape': local_shape, 'local_at': local_at,
+                'ranges': ranges}
+
+    levels, map_entries = [], []
+    for h, lo_shape, map_shapes, dims in shapes:
+        E = lo_shape[1]
+        z0, z1 = a // 2, (b + 1) // 2
+        lo, hi = max(0, z0 - 1 - p), min(E, z1 + p + 1)  # slabs.decode_halo
+        at_top = hi == E
+        El = hi - lo
+        Ll = El + (dims[0] if at_top else 0)
+        msel = []
+        for par, ms in zip(_nd.PARITY[ndim], map_shapes):
+            sel = (z0, min(z1, ms[1]))
+            msel.append((sel[0], max(sel)))
+            map_entries.append(entry(ms, sel, Ll - 1 if par[0] else El, z0 - lo))
+        levels.append({'highres': (a, b), 'out': (z0, z1), 'lowres': (lo, hi), 'maps': msel, 'at_top': at_top,
+                       'dims': tuple(dims)})
+        a, b = lo, hi
+    arrays = [entry(shapes[-1][1], (a, b), b - a, 0)] + map_entries
+    for i, e in enumerate(arrays):
+        e['index'] = i
+    return {'batch': (b0, b1), 'planes': levels[0]['highres'], 'levels': levels, 'lowres': (a, b), 'arrays': arrays,
+            'tiles_decoded': sum((e - 1) // _TILE - f // _TILE + 1 for ar in arrays for f, e, _ in ar['ranges']),
+            'tiles_total': sum(_tiles(dev.prod(ar['shape'])) for ar in arrays)}
+
+
+def _pread_exact(fd, view, offset, path):
+    if dev.pread_into(fd, view, offset) != view.size:
+        raise ValueError(f'{path}: truncated ({view.size} bytes at {offset} not present)')
+
+
+def _region_windows(fd, path, base, nbytes, rplan, plan):
+    """The table, side-information and payload windows of every range of ``plan`` read from the
+    bundle at file offset ``base`` into ONE pinned buffer.  Every value read is validated before it
+    sizes a read or a launch.  Returns ``(pinned buffer, bytes used, [(array entry, range, offsets in
+    the buffer: toff, params, bw, payload, payload_first, payload_words)], payload bytes read)``."""
+    poff, words = rplan['poff'], rplan['words']
+    if rplan['total'] > nbytes:
+        raise ValueError(f'{path}: the bundle records {rplan["total"]} bytes, the file holds {nbytes}')
+    jobs, used, payload_bytes = [], 0, 0
+    for ar in plan['arrays']:
+        i = ar['index']
+        n, code = rplan['ns'][i], rplan['codes'][i]
+        W = 8 * torch.empty(0, dtype=dev.CODE_TO_TORCH[code]).element_size()
+        side, toff = rplan['offs'][i]
+        nb, nt = -(-n // 64), _tiles(n)
+        w_first, w_end = rplan['spans'][i]
+        for rng in ar['ranges']:
+            t0, t1 = rng[0] // _TILE, (rng[1] - 1) // _TILE
+            cnt = t1 - t0 + 1
+            have = cnt + 1 if t1 + 1 < nt else cnt  # the table has no entry after the last tile
+            tab = np.empty((cnt + 1,), np.uint64)
+            _pread_exact(fd, tab[:have].view(np.uint8), base + toff + 8 * t0, path)
+            if have == cnt:
+                tab[cnt] = w_end
+            tl = [int(v) for v in tab]
+            if (t0 == 0 and tl[0] != w_first) or tl[0] < w_first or tl[-1] > w_end or w_end > words or \
+                    any(y < x or y - x > 256 * (2 * W + 2) for x, y in zip(tl, tl[1:])):
+                raise ValueError(f'{path}: tile table of array {i} is inconsistent (corrupt file)')
+            pw = tl[-1] - tl[0]
+            if poff + 4 * tl[-1] > nbytes:
+                raise ValueError(f'{path}: payload window of array {i} lies outside the file')
+            nside = min(nb, 256 * (t1 + 1)) - 256 * t0
+            o_t = used
+            o_p = o_t + 8 * (cnt + 1)
+            o_b = o_p + nside
+            o_w = (o_b + nside + 7) & ~7
+            used = (o_w + 4 * pw + 7) & ~7
+            jobs.append((ar, rng, tab, (o_t, o_p, o_b, o_w, tl[0], pw), (side + 256 * t0, nside,
+                                                                           side + ((nb + 7) & ~7) + 256 * t0)))
+            payload_bytes += 4 * pw
+    buf = dev.pinned_staging(max(used, 8), 'region')
+    hv = buf.numpy()
+    out = []
+    for ar, rng, tab, offs, (f_p, nside, f_b) in jobs:
+        o_t, o_p, o_b, o_w, w0, pw = offs
+        hv[o_t:o_t + tab.nbytes] = tab.view(np.uint8)
+        _pread_exact(fd, hv[o_p:o_p + nside], base + f_p, path)
+        _pread_exact(fd, hv[o_b:o_b + nside], base + f_b, path)
+        if pw:
+            _pread_exact(fd, hv[o_w:o_w + 4 * pw], base + poff + 4 * w0, path)
+        out.append((ar, rng, offs))
+    return buf, used, out, payload_bytes
+
+
+def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, verify=False):
+    """``decompress(path)[b0:b1, z0:z1]`` -- bit for bit, shape ``[b1 - b0, z1 - z0, H, W, C...]`` in
+    the file's sample dtype -- reading, uploading and decoding only what the selection needs.
+    ``batch=(b0, b1)`` selects items of the leading axis (any file: "tile 37" of a tiled file is
+    ``batch=(37, 38)``); ``planes=(z0, z1)`` highres planes along the first spatial axis of a volume
+    file (an image file raises ValueError).  Ranges are clamped; an empty one raises ValueError.
+    ``predictor`` as for :func:`decompress`.
+
+    Integrity: a partial read cannot check the bundle's CRC-32 and does not.  Every table entry read
+    is validated on the host, and the decode checks the side information of every tile it touches
+    (a corrupt touched tile raises ValueError); corruption in tiles the selection does not touch is
+    not noticed.  ``verify=True`` first reads and CRC-checks the whole bundle, then decodes only the
+    region.
+
+    Files without a v2 Rice bundle ('planes' files, version-1 files) are read by a full
+    :func:`decompress` plus a slice (``last_timing['partial']`` is False).  Host and device memory
+    are proportional to the selection (plus its halo planes at every level)."""
+    t0 = time.perf_counter()
+    if verify:
+        vmeta, vblob, vcrc, _ = _read(path)
+        _check_crc(path, vmeta, vcrc)
+        del vblob
+    dev.require_gpu()
+    with open(path, 'rb') as f:
+        version, meta, mlen, nbytes = _read_head(f, path)
+        fd, base = f.fileno(), _HEAD.size + mlen
+        hb = os.pread(fd, min(packing._RHEAD.size, nbytes), base)
+        partial = version >= 2 and meta.get('method') == 'rice' and hb[:4] == packing.BUNDLE_MAGIC and \
+            len(hb) == packing._RHEAD.size and struct.unpack('<H', hb[4:6])[0] == packing.RICE_VERSION
+        if not partial:  # no tile table to address: the whole file, then the slice
+            if planes is not None and meta.get('ndim') != 3:
+                raise ValueError('planes selects along the first spatial axis of a volume; an image file takes '
+                                 'batch only')
+            out = decompress(path, predictor, as_numpy)
+            b0, b1 = _clamp_range(batch, out.shape[0], 'batch')
+            z0, z1 = _clamp_range(planes, out.shape[1], 'planes')
+            out = out[b0:b1, z0:z1] if planes is not None else out[b0:b1]
+            last_timing.update(partial=False, tiles_decoded=0, tiles_total=0, payload_bytes_read=int(nbytes),
+                               bundle_bytes=int(nbytes), total=time.perf_counter() - t0)
+            return np.ascontiguousarray(out) if as_numpy else out.contiguous()
+        try:
+            plan = plan_region(meta, planes, batch)
+        except (KeyError, TypeError, IndexError) as e:
+            raise ValueError(f'{path}: corrupt metadata ({e!r})') from None
+        count = packing._RHEAD.unpack(hb)[2]
+        if not 1 <= count <= packing._MAX_ARRAYS:
+            raise ValueError(f'{path}: bad rice bundle header (count {count})')
+        head = packing._RHEAD.size + packing._RREC.size * count
+        if head > nbytes:
+            raise ValueError(f'{path}: truncated bundle')
+        hb = os.pread(fd, head, base)
+        if len(hb) != head:
+            raise ValueError(f'{path}: truncated bundle')
+        rplan = packing._rice_dec_plan(None, hb)
+        arrays = plan['arrays']
+        if [tuple(s) for s in rplan['shapes']] != [ar['shape'] for ar in arrays]:
+            raise ValueError(f'{path}: the bundle\'s arrays do not match the metadata\'s levels')
+        dtype = dev.CODE_TO_TORCH[rplan['codes'][0]]
+        pred = _decode_predictor(path, meta, predictor, dtype)
+        buf, used, jobs, payload_bytes = _region_windows(fd, path, base, nbytes, rplan, plan)
+    t1 = time.perf_counter()
+    # ---- one upload of all windows, one ranged decode per run of 32 same-dtype records into the
+    # local arrays (planes outside the selection stay unwritten: the z-region never reads them) ----
+    win = dev.empty((max(used, 8),), torch.uint8)
+    win[:used].copy_(buf[:used], non_blocking=True)
+    local = [dev.empty(ar['local_shape'], dev.CODE_TO_TORCH[rplan['codes'][ar['index']]]) for ar in arrays]
+    wp = win.data_ptr()
+    records = []
+    for ar, (first, end, dst), (o_t, o_p, o_b, o_w, w0, pw) in jobs:
+        i = ar['index']
+        t = local[i]
+        records.append((rplan['codes'][i], t.data_ptr() + dst * t.element_size(), rplan['ns'][i], first, end,
+                        wp + o_p, wp + o_b, wp + o_t, wp + o_w, w0, pw))
+    bad = torch.zeros((1,), dtype=torch.int64, device='cuda')
+    tiles = packing._launch_ranges(records, bad) if records else 0
+    # ---- the pyramid, coarsest level first, each level's z-region on its local arrays ----
+    ndim, padding = meta['ndim'], meta['padding']
+    nmaps = _nd.NMAPS[ndim]
+    coder = _nd.NATURAL_CODER[dtype]
+    dec_fn = _coder_fn(coder, ndim)
+    x = local[0]
+    for lvl in reversed(range(len(plan['levels']))):
+        L = plan['levels'][lvl]
+        maps = local[1 + nmaps * lvl:1 + nmaps * (lvl + 1)]
+        ldims = ((L['dims'][0] if L['at_top'] else 0), *L['dims'][1:])
+        E = _nd._sp(x.shape, ndim)
+        r0, r1 = L['out'][0] - L['lowres'][0], L['out'][1] - L['lowres'][0]
+        whole = r0 == 0 and r1 == E[0]
+        if _nd.fused_plan(pred, dec_fn, padding, x.dtype, ndim, 1) is not None:
+            out = dev.empty((x.shape[0], *[2 * e - 1 + d for e, d in zip(E, ldims)], *x.shape[1 + ndim:]), x.dtype)
+            region = None if whole else [(r0, r1), *[(0, e) for e in E[1:]]]
+            _nd.fused_decode_into(x, maps, ldims, pred, coder, out, ndim, region=region)
+        else:
+            if not whole:  # an opaque predictions_fn decodes the whole local array: no stray values in it
+                for m, ar in zip(maps, arrays[1 + nmaps * lvl:1 + nmaps * (lvl + 1)]):
+                    keep = m[:, ar['local_at']:ar['local_at'] + ar['sel'][1] - ar['sel'][0]].clone()
+                    m.view(torch.uint8).zero_()
+                    m[:, ar['local_at']:ar['local_at'] + keep.shape[1]] = keep
+            out = _nd.decode(pred, dec_fn, x, (maps, ldims), padding, ndim)
+        a, b = L['highres']
+        x = out[:, a - 2 * L['lowres'][0]:b - 2 * L['lowres'][0]]
+        if lvl:
+            x = x.contiguous()
+    if meta.get('sample_dtype') == 'float32':
+        x = x.contiguous().view(torch.float32)
+    nbad = int(bad.item())  # the synchronisation
+    if nbad:
+        raise ValueError(f'{path}: side information is inconsistent in {nbad} of the {tiles} tiles read (corrupt file)')
+    t2 = time.perf_counter()
+    out = dev.to_host(x) if as_numpy else x.contiguous()
+    t3 = time.perf_counter()
+    last_timing.clear()
+    last_timing.update(read=t1 - t0, device=t2 - t1, d2h=t3 - t2, total=t3 - t0, partial=True,
+                       tiles_decoded=int(tiles), tiles_total=int(plan['tiles_total']),
+                       payload_bytes_read=int(payload_bytes), bundle_bytes=int(nbytes))
+    return out

@@ -489,6 +489,119 @@ __device__ __forceinline__ void samples_from_codes(const uint32_t (&q)[8], int k
   }
 }
 
+// One wave step of the decode: the lane's 8 samples of its block (8 blocks per step, 8 lanes per
+// block) from the block's payload words ``bp`` (LDS), its k + 1 ``param`` (0: an all-zero block) and
+// its word count.  The ranged kernel's copy of the step body of rice_bundle_decode_kernel below,
+// statement for statement: calling this helper from that kernel changed its register allocation
+// (78 -> 79 VGPRs for 16-bit, 84 -> 87 for 32-bit samples), so that kernel keeps its body inline
+template <int W>
+__device__ __forceinline__ void decode_block8(int param, const int words, const uint32_t* const bp, const int lane,
+                                              const int j, uint32_t (&wout)[Sw<W>::NW]) {
+  constexpr int NP = Sw<W>::NP, NW = Sw<W>::NW;
+  const int k = param > 0 ? param - 1 : 0;
+  const int uw = param > 0 ? words - 2 * k : 0;
+  uint32_t Z[NP][2];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int b = 8 * p + j;
+    const bool hv = param > 0 && b < k;
+    Z[p][0] = hv ? bp[2 * b] : 0u;
+    Z[p][1] = hv ? bp[2 * b + 1] : 0u;
+  }
+  // every block of the wave step with k <= 8 (the usual residual map): plane groups from 1 up
+  // hold no stored planes (all zero), so only group 0 is transposed back
+  const bool lo8 = __all(param <= 9);
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    if (p > 0 && lo8) continue;
+    xtr8(Z[p][0], Z[p][1], j);
+    tr8x8(Z[p][0], Z[p][1]);
+  }
+  uint32_t lowv[NW];
+  scatter_bytes<W>(Z, lowv);
+  const uint32_t* us = bp + 2 * k;
+  uint32_t q[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) q[e] = 0u;
+  // lane j's first code follows terminator 8j - 1.  Streams of at most 8 words (the usual case):
+  // lane m holds word m and its popcount c_m; with the group's inclusive counts cum_m, the word
+  // holding terminator 8j - 1 is #{m : cum_m >> 3 < j}, counted for all j at once as nibble j of
+  // a group sum (lane m adds 1 to the nibbles j > cum_m >> 3); then one select in that word.
+  // No loop and no LDS round trip per word (a walk word by word measured slower)
+  uint32_t pos8 = 0;
+  const bool short_stream = __all(!(param > 0) || uw <= 8);
+  if (short_stream) {
+    const uint32_t wm = (param > 0 && j < uw) ? us[j] : 0u;
+    const uint32_t cm = __builtin_popcount(wm);
+    const uint32_t cum = group8_incl(cm, lane & 8);
+    const uint32_t d = cum >> 3;
+    const uint32_t f = d >= 7u ? 0u : 0x11111110u & (~0u << (4u * (d + 1u)));
+    const uint32_t F = group8_sum(f, j);
+    const uint32_t wi = (F >> (4 * j)) & 15u;  // j > 0
+    const int src = (lane & ~7) | (int)min(wi, 7u);
+    const uint32_t wsel = (uint32_t)__shfl((int)wm, src, 64);
+    const uint32_t before = (uint32_t)__shfl((int)(cum - cm), src, 64);
+    pos8 = j == 0 ? 0u : wi < 8u && wi < (uint32_t)uw ? 32u * wi + select32(wsel, 8u * j - 1u - before) + 1u
+                                                       : 32u * (uint32_t)uw;
+  }
+  if (param > 0 && uw > 0) {
+    uint32_t pos = pos8;
+    if (!short_stream && j > 0) {
+      const uint32_t r = 8u * j - 1u;
+      uint32_t acc = 0, word = 0;
+      int wi = 0;
+      for (; wi < uw; ++wi) {
+        word = us[wi];
+        const uint32_t c = __builtin_popcount(word);
+        if (acc + c > r) break;
+        acc += c;
+      }
+      pos = wi < uw ? 32u * wi + select32(word, r - acc) + 1u : 32u * uw;
+    }
+    int wi = (int)(pos >> 5);
+    const uint32_t sh = pos & 31u;
+    const uint32_t a0 = wi < uw ? us[wi] : 0u, b0 = wi + 1 < uw ? us[wi + 1] : 0u;
+    uint32_t x = __builtin_amdgcn_alignbit(b0, a0, sh);
+    if (__builtin_popcount(x) >= 8) {  // the lane's 8 codes within 32 bits (the common case)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const uint32_t tz = (uint32_t)__builtin_ctz(x);
+        q[e] = tz;
+        x = (x >> tz) >> 1;
+      }
+    } else {
+      const uint32_t c0 = wi + 2 < uw ? us[wi + 2] : 0u;
+      uint64_t win = ((uint64_t)__builtin_amdgcn_alignbit(c0, b0, sh) << 32) | x;
+      if (__builtin_popcountll(win) >= 8) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const uint32_t tz = (uint32_t)__builtin_ctzll(win);
+          q[e] = tz;
+          win = (win >> tz) >> 1;
+        }
+      } else {
+        uint32_t cur = wi < uw ? us[wi] >> sh : 0u;
+        uint32_t base = pos;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          while (cur == 0u && wi + 1 < uw) {
+            ++wi;
+            cur = us[wi];
+            base = 32u * wi;
+          }
+          if (cur == 0u) break;  // a corrupt stream with fewer than 64 terminators
+          const uint32_t tz = __builtin_ctz(cur);
+          q[e] = base + tz - pos;
+          pos = base + tz + 1u;
+          cur = tz == 31u ? 0u : cur >> (tz + 1u);
+          base = pos;
+        }
+      }
+    }
+  }
+  samples_from_codes<W>(q, k, lowv, param > 0, wout);
+}
+
 template <int W>
 __global__ void __launch_bounds__(256) rice_bundle_decode_kernel(RArrs A, int64_t tile_begin,
                                                                const uint8_t* __restrict__ blob,
@@ -686,6 +799,143 @@ __global__ void __launch_bounds__(256) rice_bundle_decode_kernel(RArrs A, int64_
   }
 }
 
+// ---- decode of sample ranges (rice_bundle_decode_ranges_kernel): one workgroup per tile a range
+// touches, the tile shape, lane layout, block decode and per-tile checks of the kernel above.  A
+// record's side information, table and payload are separate pointers, so they may be windows of a
+// bundle that is mostly not on the device.  The per-block word offsets inside a tile still take all
+// of the tile's bw (side information only); wave steps whose 8 blocks lie wholly outside
+// [first, end) -- wave-uniform -- skip the payload staging and the decode; stores are clipped at
+// both ends ----
+struct RRanges {
+  kmp_rice_range r[kMaxArr];
+  int count;
+};
+
+// the lane's samples i0 .. i0 + 7 of the array into out[i - first], first <= i < end: lanes wholly
+// inside by the unaligned vector stores of store8s, the others element by element
+template <int W>
+__device__ __forceinline__ void store8s_clip(void* out, int64_t first, int64_t end, int64_t i0,
+                                             const uint32_t (&w)[Sw<W>::NW]) {
+  if (i0 >= first && i0 + 8 <= end) {
+    store8s<W>(out, end - first, i0 - first, w);
+    return;
+  }
+  for (int e = 0; e < 8; ++e) {
+    const int64_t i = i0 + e;
+    if (i < first || i >= end) continue;
+    const uint32_t v = W == 32 ? w[e] : (w[(e * W) / 32] >> ((e * W) % 32)) & ((1u << (W & 31)) - 1u);
+    store_sample<W>(out, i - first, v);
+  }
+}
+
+template <int W>
+__global__ void __launch_bounds__(256) rice_bundle_decode_ranges_kernel(RRanges A,
+                                                                      unsigned long long* __restrict__ bad_out) {
+  constexpr int NW = Sw<W>::NW;
+  constexpr int SPAN = 8 * (2 * W + 2);
+  constexpr int S = kTileSteps;
+  constexpr int64_t kTileSamples = (int64_t)kTileBlocks * kBlock;
+  __shared__ uint32_t span_lds[4][S * SPAN];
+  __shared__ uint32_t wsum[4];
+  __shared__ uint32_t wbad[4];
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, j = lane & 7, g8 = lane >> 3;
+  // the record of this workgroup's tile (uniform): records own consecutive runs of the grid
+  int a = 0;
+  int64_t tl = blockIdx.x;  // the tile's index among the record's touched tiles
+  while (a + 1 < A.count) {
+    const int64_t nt = (A.r[a].end - 1) / kTileSamples - A.r[a].first / kTileSamples + 1;
+    if (tl < nt) break;
+    tl -= nt;
+    ++a;
+  }
+  const kmp_rice_range& R = A.r[a];
+  const int64_t T0 = R.first / kTileSamples;
+  const int64_t nb = (R.n + kBlock - 1) / kBlock;
+  const int64_t wblk0 = tl * kTileBlocks + wv * 8 * S;   // the wave's first block in the side windows
+  const int64_t blk0 = T0 * kTileBlocks + wblk0;          // ... and in the array
+  // ---- side information, checks and per-block offsets as in the whole-bundle kernel; the steps
+  // this range needs and the word span [lo, hi) of the wave they cover ----
+  int prm[S], wds[S];
+  uint32_t bex[S], stp[S];
+  bool need[S];
+  uint32_t wtot = 0, lo = 0, hi = 0;
+  bool bad = false, any_need = false;
+#pragma unroll
+  for (int st = 0; st < S; ++st) {
+    const int64_t blk = blk0 + 8 * st + g8;
+    const bool has = blk < nb;
+    prm[st] = has ? R.params[wblk0 + 8 * st + g8] : 0;
+    wds[st] = has ? R.bw[wblk0 + 8 * st + g8] : 0;
+  }
+#pragma unroll
+  for (int st = 0; st < S; ++st) {
+    const int kk = prm[st] - 1;
+    const bool b = prm[st] == 0 ? wds[st] != 0 : (kk >= W || wds[st] < 2 * kk + 2 || wds[st] > 2 * W + 2);
+    bad |= b;
+    if (b) wds[st] = 0;
+    uint32_t stot;
+    bex[st] = wave_groups_excl((uint32_t)wds[st], lane, &stot);
+    stp[st] = wtot;
+    const int64_t s0 = (blk0 + 8 * st) * kBlock;  // the step's samples [s0, s0 + 512)
+    need[st] = s0 < R.end && s0 + 8 * kBlock > R.first;
+    if (need[st]) {
+      if (!any_need) lo = wtot;
+      any_need = true;
+      hi = wtot + stot;
+    }
+    wtot += stot;
+  }
+  const bool wave_bad = __any(bad);
+  if (lane == 0) {
+    wsum[wv] = wtot;
+    wbad[wv] = wave_bad;
+  }
+  __syncthreads();
+  const uint64_t base = R.payload_first;
+  const uint64_t start = R.toff[tl];
+  const uint64_t end = R.toff[tl + 1];
+  const uint32_t agg = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+  // every read below lies in payload[start - base, end - base), inside payload_words
+  const bool tile_bad = wbad[0] || wbad[1] || wbad[2] || wbad[3] || start < base || end < start ||
+                        end - base > R.payload_words || start + agg != end;
+  if (tile_bad && tid == 0) atomicAdd(bad_out, 1ull);
+  uint32_t wbase = 0;
+  for (int q = 0; q < wv; ++q) wbase += wsum[q];
+  uint32_t* const wspan = span_lds[wv];
+  if (any_need) {
+    const uint32_t* src = R.payload + ((start - base) + wbase);
+    const int i_lo = tile_bad ? 0 : (int)min(lo, (uint32_t)(S * SPAN));
+    const int i_hi = tile_bad ? 0 : (int)min(hi, (uint32_t)(S * SPAN));
+    for (int i0 = i_lo; i0 < i_hi; i0 += 64 * 8) {
+      uint32_t v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + 64 * u + lane;
+        v[u] = i < i_hi ? src[i] : 0u;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + 64 * u + lane;
+        if (i < i_hi) wspan[i] = v[u];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+#pragma unroll
+  for (int st = 0; st < S; ++st) {
+    if (!need[st]) continue;  // wave-uniform
+    int param = tile_bad ? 0 : prm[st];
+    const int words = tile_bad ? 0 : wds[st];
+    const uint32_t* const bp = wspan + (tile_bad ? 0 : stp[st] + bex[st]);
+    uint32_t wout[NW];
+    decode_block8<W>(param, words, bp, lane, j, wout);
+    const int64_t blk = blk0 + 8 * st + g8;
+    if (blk < nb) store8s_clip<W>(R.samples, R.first, R.end, blk * 64 + j * 8, wout);
+  }
+}
+
 // side information a blob may hold (one workgroup; written next to the scan's total): planes --
 // widths <= W; rice -- k < W, an all-zero block has no payload, a coded block holds its 2k plane
 // words and >= 2 unary words, at most 2W + 2 in all.  The count of violating blocks is read back
@@ -820,6 +1070,31 @@ int kmp_rice_bundle_decode(int32_t dtype, const kmp_rice_array* arrays, int32_t 
   else if (W == 16) rc::rice_bundle_decode_kernel<16><<<(unsigned)tiles, 256, 0, s>>>(A, tile_begin, bundle, payload_off, payload_words, bad);
   else rc::rice_bundle_decode_kernel<32><<<(unsigned)tiles, 256, 0, s>>>(A, tile_begin, bundle, payload_off, payload_words, bad);
   return check_launch("rice_bundle_decode");
+}
+
+int kmp_rice_bundle_decode_ranges(int32_t dtype, const kmp_rice_range* ranges, int32_t count,
+                                  unsigned long long* bad, kmp_stream_t stream) {
+  const int W = pk::sample_bits(dtype);
+  KMP_REQUIRE(W > 0, "rice ranges: unsupported dtype");
+  KMP_REQUIRE(ranges && bad && count >= 1 && count <= rc::kMaxArr, "rice ranges: 1 .. 32 records per call");
+  constexpr int64_t kTileSamples = (int64_t)rc::kTileBlocks * pk::kBlock;
+  rc::RRanges A{};
+  A.count = count;
+  int64_t tiles = 0;
+  for (int i = 0; i < count; ++i) {
+    const kmp_rice_range& r = ranges[i];
+    KMP_REQUIRE(r.samples && r.n > 0 && r.first >= 0 && r.first < r.end && r.end <= r.n, "rice ranges: bad range");
+    KMP_REQUIRE(r.params && r.bw && r.toff && (r.payload || r.payload_words == 0), "rice ranges: null window");
+    KMP_REQUIRE((uintptr_t)r.toff % 8 == 0 && (uintptr_t)r.payload % 4 == 0, "rice ranges: misaligned window");
+    A.r[i] = r;
+    tiles += (r.end - 1) / kTileSamples - r.first / kTileSamples + 1;
+  }
+  KMP_REQUIRE(tiles < ((int64_t)1 << 31), "rice ranges: too many tiles in one call");
+  hipStream_t s = (hipStream_t)stream;
+  if (W == 8) rc::rice_bundle_decode_ranges_kernel<8><<<(unsigned)tiles, 256, 0, s>>>(A, bad);
+  else if (W == 16) rc::rice_bundle_decode_ranges_kernel<16><<<(unsigned)tiles, 256, 0, s>>>(A, bad);
+  else rc::rice_bundle_decode_ranges_kernel<32><<<(unsigned)tiles, 256, 0, s>>>(A, bad);
+  return check_launch("rice_bundle_decode_ranges");
 }
 
 }  // extern "C"

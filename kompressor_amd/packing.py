@@ -442,7 +442,115 @@ def _rice_dec_plan(b, hb):
         runs.append((first, count, tile_begin, codes[first]))
         tile_begin += sum(tiles[first:first + count])
     return {'ns': ns, 'offs': offs, 'shapes': shapes, 'codes': codes, 'dims': tuple(int(d) for d in dims[:nsp]), 'poff': poff,
-            'words': words, 'total': total, 'T': sum(tiles), 'runs': runs}
+            'words': words, 'total': total, 'T': sum(tiles), 'runs': runs,
+            'spans': [(r[15], r[16]) for r in recs]}  # each array's (first word, end word)
+
+
+# ---------------------------------------------------------------------------------------------
+# sample ranges of a rice bundle (kmp_rice_bundle_decode_ranges): only the tiles a range touches
+# are decoded; the side information, the tile table and the payload of a record are separate
+# pointers, into a resident bundle (unpack_ranges) or at windows read from a file
+# (container.read_region)
+# ---------------------------------------------------------------------------------------------
+
+_TILE_SAMPLES = 64 * _TILE_BLOCKS
+
+
+def _range_tiles(first, end):
+    """``(T0, T1)``: the first and last tile samples ``[first, end)`` touch."""
+    return first // _TILE_SAMPLES, (end - 1) // _TILE_SAMPLES
+
+
+def _launch_ranges(records, bad):
+    """The ranged decode of ``records`` -- tuples ``(dtype code, out ptr, n, first, end, params ptr,
+    bw ptr, toff ptr, payload ptr, payload_first, payload_words)`` -- in runs of one dtype, at most
+    32 per launch; no synchronisation.  Returns the tiles decoded."""
+    tiles, i = 0, 0
+    while i < len(records):
+        k = i + 1
+        while k < len(records) and k - i < 32 and records[k][0] == records[i][0]:
+            k += 1
+        arr = (_lib.RiceRange * (k - i))()
+        for q, r in enumerate(records[i:k]):
+            (_, arr[q].samples, arr[q].n, arr[q].first, arr[q].end, arr[q].params, arr[q].bw, arr[q].toff,
+             arr[q].payload, arr[q].payload_first, arr[q].payload_words) = r
+            t0, t1 = _range_tiles(r[3], r[4])
+            tiles += t1 - t0 + 1
+        check(lib.kmp_rice_bundle_decode_ranges(records[i][0], arr, k - i, bad.data_ptr(), dev.stream()),
+              'rice ranges')
+        i = k
+    return tiles
+
+
+def unpack_ranges(blob, requests):
+    """Sample ranges of the arrays of a resident v2 Rice bundle: ``requests`` is a list of
+    ``(array_index, first, end)`` flat sample ranges (``0 <= first < end <= n``); returns a list of
+    1-D arrays, ``result[i] == unpack_encoded(blob) array[array_index].reshape(-1)[first:end]`` bit
+    for bit (numpy in -> numpy out).  Only the 16384-sample tiles a range touches are decoded (one
+    launch per run of at most 32 same-dtype requests, one synchronisation for the per-tile
+    consistency counter: a corrupt touched tile raises ValueError, an untouched one is not looked
+    at).  'planes' blobs have no tile table and raise ValueError."""
+    b, kind = dev.to_device(blob)
+    if b.dtype != torch.uint8 or b.dim() != 1:
+        raise ValueError('a blob is a 1-D uint8 array')
+    if b.data_ptr() % 8:
+        b = b.clone()
+    hb = _head_bytes(b, 4096)
+    if hb[:4] != BUNDLE_MAGIC or len(hb) < 6 or struct.unpack('<H', hb[4:6])[0] != RICE_VERSION:
+        raise ValueError("not a v2 rice bundle ('planes' blobs keep no tile table: unpack them whole)")
+    count = _RHEAD.unpack(hb[:_RHEAD.size])[2] if len(hb) >= _RHEAD.size else 0
+    head = _RHEAD.size + _RREC.size * count if 1 <= count <= _MAX_ARRAYS else _RHEAD.size
+    if len(hb) < head:
+        hb = b[:head].cpu().numpy().tobytes()
+    key = bytes(hb[:head])
+    plan = _DEC_PLANS.get(key)
+    if plan is None:
+        plan = _remember(_DEC_PLANS, key, _rice_dec_plan(b, hb))
+    if plan['total'] > b.numel():
+        raise ValueError(f'truncated bundle ({b.numel()} < {plan["total"]} bytes)')
+    reqs = []
+    for req in requests:
+        ai, first, end = (int(v) for v in req)
+        if not 0 <= ai < len(plan['ns']):
+            raise ValueError(f'array index {ai} outside the bundle\'s {len(plan["ns"])} arrays')
+        if not 0 <= first < end <= plan['ns'][ai]:
+            raise ValueError(f'range [{first}, {end}) outside the {plan["ns"][ai]} samples of array {ai}')
+        reqs.append((ai, first, end))
+    if not reqs:
+        return []
+    # a range reaching an array's last tile closes its table window with the record's end word
+    # (the table itself has no entry after the last tile): those windows are copied beside it
+    base, closing, slots = b.data_ptr(), [], []
+    for ai, first, end in reqs:
+        t0, t1 = _range_tiles(first, end)
+        if t1 + 1 == int(lib.kmp_rice_tiles(plan['ns'][ai])):
+            slots.append(len(closing))
+            closing += [0] * (t1 - t0 + 1) + [plan['spans'][ai][1]]
+        else:
+            slots.append(None)
+    tt = torch.tensor(closing, dtype=torch.int64).to('cuda') if closing else None
+    outs, records = [], []
+    for (ai, first, end), slot in zip(reqs, slots):
+        n, code = plan['ns'][ai], plan['codes'][ai]
+        side, toff = plan['offs'][ai]
+        t0, t1 = _range_tiles(first, end)
+        if slot is None:
+            tptr = base + toff + 8 * t0
+        else:
+            nt = t1 - t0 + 1
+            tt[slot:slot + nt].view(torch.uint8).copy_(b[toff + 8 * t0:toff + 8 * (t1 + 1)])
+            tptr = tt.data_ptr() + 8 * slot
+        out = dev.empty((end - first,), dev.CODE_TO_TORCH[code])
+        outs.append(out)
+        nb8 = _pad8(int(lib.kmp_pack_blocks(n)))
+        records.append((code, out.data_ptr(), n, first, end, base + side + _TILE_BLOCKS * t0,
+                        base + side + nb8 + _TILE_BLOCKS * t0, tptr, base + plan['poff'], 0, plan['words']))
+    bad = torch.zeros((1,), dtype=torch.int64, device='cuda')
+    _launch_ranges(records, bad)
+    nbad = int(bad.item())  # the one synchronisation
+    if nbad:
+        raise ValueError(f'rice bundle side information is inconsistent in {nbad} of the tiles read (corrupt bundle)')
+    return [dev.from_device(o, kind) for o in outs]
 
 
 # ---------------------------------------------------------------------------------------------
