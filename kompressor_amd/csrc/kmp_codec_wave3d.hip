@@ -46,6 +46,8 @@ struct W3 {
   int32_t nt_nodes; // plane kernel: 1 = non-temporal node-row loads, 0 = default policy (L2-shared halo)
   int64_t nB;       // tiles in the batch (debug-build bounds checks only)
   int32_t nvblk;    // blocks (= workgroups launched)
+  int32_t rev;      // 1: blocks are coded last-first (dispatch-order block v codes block nvblk - 1 - v)
+  int32_t stc_from; // encode: the first dispatch-order block whose lowres / map stores are cached
 };
 
 // rows a lane reads for one node plane: its own, and (wave's first / last row) one halo row;
@@ -63,17 +65,25 @@ struct OutRows {
   uint2 mv[7];
 };
 
-// Store policy (STC, stp8 in kmp_wave.h), chosen on the pipelines that follow an encode at C3
-// (tools/pipeline_rows.py, profiles/round3/pipeline_store_policy_r3.log; DESIGN §5 "pipeline"):
-// the encode's lowres and maps are stored non-temporal.  Cached (MALL-allocating) stores let a
-// decode that immediately re-reads the same maps find part of them in the MALL (bench.py's
-// encode -> decode loop: 177 -> 171 us per pair), but their dirty lines drain during the next
-// encode when encodes run back to back (a producer of chunks: 85 -> 103 us per encode), and encode
-// -> Rice pack / Rice unpack -> decode are within 3 us either way.  The decode's highres is
-// non-temporal too (cached: +7 us on the next encode).  KMP_W3_ST_ENC=1: cached encode stores.
+// Store policy (stp8 in kmp_wave.h), chosen on the pipelines that follow an encode at C3
+// (tools/pipeline_rows.py, profiles/pipeline_order_tail*.log; DESIGN §5 "pipeline").  Storing ALL
+// of the encode's lowres and maps cached (MALL-allocating, KMP_W3_ST_ENC=1) lets a decode that
+// immediately re-reads them find part of them in the MALL (bench.py's encode -> decode loop:
+// 174 -> 166 us per pair), but the dirty lines drain during the next encode when encodes run back
+// to back (a producer of chunks: 84 -> 96 us per encode).  Storing only the blocks dispatched last
+// cached (W3::stc_from: the last KMP_W3_ST_TAIL KiB of output, at most half of the call's blocks;
+// default 128 MiB) keeps most of the pair's gain (171 -> 163 us) and costs the producer nothing
+// (84 -> 83.5 us); encode -> Rice pack / Rice unpack -> decode are within their noise either way.
+// The rest of the encode's output and the decode's highres are non-temporal (cached highres: +7 us
+// on the next encode).  The two arms of the store branch must stay apart in the ISA (the u16 PL = 2
+// encode: 16 stores with ``nt``, 16 without): compilers merge arms that differ only in the hint.
+//
+// W3::rev (KMP_W3_DEC_REV=1) lets the decode walk its blocks last-first, to start with the bytes
+// written last.  Measured, it does not help: the pair is 1 - 2 us slower with it alone and 4 us
+// slower with it beside the cached tail, so the default is the forward order.
 
 // WPE: the amdgpu_waves_per_eu register budget (PL = 2 encode: 3 waves / SIMD without spills).
-template <typename T, bool DEC, int PL, bool ONE, bool STC>
+template <typename T, bool DEC, int PL, bool ONE>
 __device__ __forceinline__ void wave3d_plane_body(const W3& a, int vblk) {
   constexpr int VX = 8 / (int)sizeof(T);
   constexpr uint32_t MASK = sizeof(T) == 2 ? 0xffffu : 0xffu;
@@ -85,6 +95,10 @@ __device__ __forceinline__ void wave3d_plane_body(const W3& a, int vblk) {
   const int tx = lane & (a.txn - 1);          // txn: a power of two (host)
   const int r = lane >> __builtin_ctz(a.txn);
   const int X = tx * VX;
+  const bool stc = !DEC && vblk >= a.stc_from;  // wave-uniform: the tail of the dispatch order
+  // last-first: with the XCD order nvblk is a multiple of 8, so XCD x still codes whole tiles
+  // (those of XCD 7 - x in forward order), its blocks in descending order
+  if (a.rev) vblk = a.nvblk - 1 - vblk;
   int blk = xcd_block(vblk, a.xcd_per);  // tile-per-XCD order: the z-halo neighbours share an L2
   const int yg = blk % a.nyg;
   blk /= a.nyg;
@@ -325,19 +339,25 @@ __device__ __forceinline__ void wave3d_plane_body(const W3& a, int vblk) {
         res[5][i] = (el16<T>(Oc.e1, 2 * i) - pred[5][i]) & MASK;      // Y  (0,1,0)
         res[6][i] = (el16<T>(e0, 2 * i + 1) - pred[6][i]) & MASK;     // X  (0,0,1)
       }
-      KMP_SPAN((const T*)a.lo_out, (const T*)a.lo_out + b * (int64_t)a.Ez * lplane + c * lplane + lo_own, VX,
-               a.nB * a.Ez * lplane);
-      stp8<STC>((T*)a.lo_out + b * (int64_t)a.Ez * lplane + c * lplane + lo_own, pack8<T, VX>(lov));
+      T* lp = (T*)a.lo_out + b * (int64_t)a.Ez * lplane + c * lplane + lo_own;
+      KMP_SPAN((const T*)a.lo_out, (const T*)lp, VX, a.nB * a.Ez * lplane);
+      // one uniform branch around the plane's 8 stores, so that each flavour is straight-line code
+      auto put = [&](auto cached) __attribute__((always_inline)) {
+        constexpr bool STC = decltype(cached)::value;
+        stp8<STC>(lp, pack8<T, VX>(lov));
 #pragma unroll
-      for (int k = 0; k < 7; ++k) {
-        int par[3];
-        map_parity(3, k, par);
-        if (mok_y[k] && (!par[0] || vz1)) {
-          KMP_SPAN((const T*)a.maps.p[k], mbase[k] + c * mplane[k], VX,
-                   a.nB * (par[0] ? a.Lcz : a.Ez) * mplane[k]);
-          stp8<STC>((T*)mbase[k] + c * mplane[k], pack8<T, VX>(res[k]));
+        for (int k = 0; k < 7; ++k) {
+          int par[3];
+          map_parity(3, k, par);
+          if (mok_y[k] && (!par[0] || vz1)) {
+            KMP_SPAN((const T*)a.maps.p[k], mbase[k] + c * mplane[k], VX,
+                     a.nB * (par[0] ? a.Lcz : a.Ez) * mplane[k]);
+            stp8<STC>((T*)mbase[k] + c * mplane[k], pack8<T, VX>(res[k]));
+          }
         }
-      }
+      };
+      if (stc) put(std::true_type{});
+      else put(std::false_type{});
     } else {
       const OR& Oc = O[u];
       uint32_t own[VX], dv[7][VX];
@@ -364,9 +384,9 @@ __device__ __forceinline__ void wave3d_plane_body(const W3& a, int vblk) {
 // live across iterations, the loop's kernel arguments overflowed the scalar registers (29 / 32 SGPRs
 // spilled into VGPR lanes: 98 / 72 v_readlane per encode / decode wave); without it none spill and
 // the waves issue 849 -> 731 / 818 -> 713 VALU instructions (round 5)
-template <typename T, bool DEC, int PL, int WPE, bool ONE, bool STC = false>
+template <typename T, bool DEC, int PL, int WPE, bool ONE>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) wave3d_plane_kernel(W3 a) {
-  wave3d_plane_body<T, DEC, PL, ONE, STC>(a, (int)blockIdx.x);
+  wave3d_plane_body<T, DEC, PL, ONE>(a, (int)blockIdx.x);
 }
 
 }  // namespace w3
@@ -374,6 +394,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 // ------------------------------------------------------------------------------------------
 // Host: eligibility + launch geometry
 // ------------------------------------------------------------------------------------------
+// Defaults of KMP_W3_DEC_REV and KMP_W3_ST_TAIL (KiB), chosen on the pipeline rows
+constexpr int kW3DecRev = 0;
+constexpr int kW3StTailKiB = 128 * 1024;
+
 template <typename T>
 static bool wave3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred, const kmp_region* region,
                             int pl, w3::W3& a, dim3& grid, dim3& block) {
@@ -409,25 +433,45 @@ static bool wave3d_geometry(const Geo& g, int64_t B, int64_t C, const kmp_predic
   return nblk < ((int64_t)1 << 31);
 }
 
-template <typename T, bool DEC, bool STC>
-static void launch_wave3d_s(int pl, dim3 grid, dim3 block, hipStream_t stream, const w3::W3& a) {
+template <typename T, bool DEC>
+static void launch_wave3d(int pl, dim3 grid, dim3 block, hipStream_t stream, const w3::W3& a) {
   // PL = 2 at 3 waves / SIMD is the measured optimum at C3 (profiles/round1/kprof_wave3d.log):
   // PL = 1 re-reads twice the z halo per output plane; forcing 4 waves / SIMD spills
   if (a.rows == 1) {  // 64 lanes per output row (wide volumes): both halo rows per lane
-    if (pl == 1) w3::wave3d_plane_kernel<T, DEC, 1, 4, true, STC><<<grid, block, 0, stream>>>(a);
-    else w3::wave3d_plane_kernel<T, DEC, 2, 3, true, STC><<<grid, block, 0, stream>>>(a);
+    if (pl == 1) w3::wave3d_plane_kernel<T, DEC, 1, 4, true><<<grid, block, 0, stream>>>(a);
+    else w3::wave3d_plane_kernel<T, DEC, 2, 3, true><<<grid, block, 0, stream>>>(a);
   } else if (pl == 1) {
-    w3::wave3d_plane_kernel<T, DEC, 1, 4, false, STC><<<grid, block, 0, stream>>>(a);
+    w3::wave3d_plane_kernel<T, DEC, 1, 4, false><<<grid, block, 0, stream>>>(a);
   } else {
-    w3::wave3d_plane_kernel<T, DEC, 2, 3, false, STC><<<grid, block, 0, stream>>>(a);
+    w3::wave3d_plane_kernel<T, DEC, 2, 3, false><<<grid, block, 0, stream>>>(a);
   }
 }
 
-template <typename T, bool DEC>
-static void launch_wave3d(int pl, dim3 grid, dim3 block, hipStream_t stream, const w3::W3& a) {
-  // non-temporal stores in both directions; KMP_W3_ST_ENC=1: the encode's cached (stp8)
-  if (!DEC && opt(OPT_W3_ST_ENC, 0)) launch_wave3d_s<T, DEC, true>(pl, grid, block, stream, a);
-  else launch_wave3d_s<T, DEC, false>(pl, grid, block, stream, a);
+// cached stores must not be chosen for outputs in (zero-copy) pinned host memory: true only for
+// memory of the device itself
+static bool is_device_memory(const void* p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return at.type == hipMemoryTypeDevice;
+}
+
+// The first dispatch-order block of the encode whose lowres / map stores are cached
+// (MALL-allocating): KMP_W3_ST_ENC = 1 / 0 all / none of them; unset, the blocks that write the
+// last KMP_W3_ST_TAIL KiB of the call's output (8 arrays of about Ey * Ex samples per output plane)
+template <typename T>
+static int wave3d_stc_from(const w3::W3& a, const void* out) {
+  const int st = opt(OPT_W3_ST_ENC, -1);
+  if (st >= 0) return st ? 0 : a.nvblk;
+  const int64_t tail = (int64_t)opt(OPT_W3_ST_TAIL, kW3StTailKiB) * 1024;
+  if (tail <= 0 || !is_device_memory(out)) return a.nvblk;
+  const int64_t per_blk = 8 * (int64_t)sizeof(T) * a.slab * std::min(a.nwv * a.rows, a.Ey) * a.Ex;
+  // at most half of the call's blocks: a producer pays for every cached byte (its dirty lines
+  // drain under the next kernel), whatever the size of the batch
+  const int64_t n = std::min(ceil_div(tail, per_blk), (int64_t)(a.nvblk + 1) / 2);
+  return a.nvblk - (int)n;
 }
 
 template <typename T, bool DEC>
@@ -438,6 +482,8 @@ int try_wave3d(const CodecCall<T, DEC>& c) {
   if (!wave3d_geometry<T>(c.g, c.B, c.C, c.pred, c.region, pl, a, grid, block)) return KMP_ERR_UNSUPPORTED;
   if (!ptrs_aligned(c, 16, 8, 7)) return KMP_ERR_UNSUPPORTED;
   bind(a, c);
+  if constexpr (DEC) a.rev = opt(OPT_W3_DEC_REV, kW3DecRev) ? 1 : 0;
+  else a.stc_from = wave3d_stc_from<T>(a, c.out);
   launch_wave3d<T, DEC>(pl, grid, block, c.stream, a);
   return check_launch(DEC ? "wave3d_decode" : "wave3d_encode");
 }

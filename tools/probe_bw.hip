@@ -6,9 +6,12 @@
 // 3. merge8: the inverse (decode's shape)
 // ./tools/probe_bw c2: only the C2-sized probes -- 64 MiB -> 64 MiB copies alternating X -> M and
 //    M -> R like bench.py's encode / decode pairs (the 192 MiB working set fits the 256 MiB MALL)
+// ./tools/probe_bw c3order: the same pair in the codec's block order, with the consumer's order and
+//    the producer's store policy varied (see c3order below; log: profiles/probe_c3order.log)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <cstring>
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -135,7 +138,130 @@ __global__ void __launch_bounds__(256) codec_shape(const uint16_t* __restrict__ 
   }
 }
 
+// c3order: split8 / merge8 with the codec's block order instead of a grid-stride loop.  The 256 MiB
+// are 512 tiles of 16 blocks; a block moves 32 KiB (8 x 16 B per lane in, 4 KiB into each of the 8
+// streams out, or the inverse), all loads before the first store.  Blocks follow the tile-per-XCD
+// order (xcd_block in kmp_wave.h); ``rev`` walks them last-first; stores of dispatch-order blocks
+// >= ``stc_from`` use the default policy (MALL-allocating), the others are non-temporal.
+constexpr int kTiles = 512, kPerTile = 16, kOrderBlocks = kTiles * kPerTile;
+__device__ __forceinline__ int order_block(int v, int rev) {
+  if (rev) v = kOrderBlocks - 1 - v;
+  const int x = v % 8, k = v / 8;
+  return ((k / kPerTile) * 8 + x) * kPerTile + (k % kPerTile);
+}
+__global__ void __launch_bounds__(256) split8t(const u32x4* __restrict__ a, u32x2* __restrict__ out, int64_t per,
+                                               int rev, int stc_from) {
+  const bool stc = (int)blockIdx.x >= stc_from;  // uniform
+  const int blk = order_block((int)blockIdx.x, rev);
+  u32x4 v[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) v[r] = __builtin_nontemporal_load(a + (int64_t)blk * 2048 + r * 256 + threadIdx.x);
+  const int64_t o = (int64_t)blk * 512 + threadIdx.x;
+  // the two arms differ only in the stores' cache policy, and the compiler merges such arms into one
+  // set of plain stores (it drops the non-temporal hint: seen in this kernel's ISA); the distinct
+  // asm comments keep them apart -- check with ``hipcc -S``: 16 stores with ``nt``, 16 without
+  if (stc) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      asm volatile("; cached" ::: "memory");
+      out[r * per + o] = u32x2{v[r].x, v[r].y};
+      out[r * per + o + 256] = u32x2{v[r].z, v[r].w};
+    }
+    asm volatile("; cached" ::: "memory");
+  } else {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      asm volatile("; streaming" ::: "memory");
+      __builtin_nontemporal_store(u32x2{v[r].x, v[r].y}, out + r * per + o);
+      __builtin_nontemporal_store(u32x2{v[r].z, v[r].w}, out + r * per + o + 256);
+    }
+    asm volatile("; streaming" ::: "memory");
+  }
+}
+__global__ void __launch_bounds__(256) merge8t(const u32x2* __restrict__ in, u32x4* __restrict__ b, int64_t per,
+                                               int rev) {
+  const int blk = order_block((int)blockIdx.x, rev);
+  const int64_t o = (int64_t)blk * 512 + threadIdx.x;
+  u32x2 lo[8], hi[8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    lo[r] = __builtin_nontemporal_load(in + r * per + o);
+    hi[r] = __builtin_nontemporal_load(in + r * per + o + 256);
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r)
+    __builtin_nontemporal_store(u32x4{lo[r].x, lo[r].y, hi[r].x, hi[r].y}, b + (int64_t)blk * 2048 + r * 256 + threadIdx.x);
+}
+
+// ./tools/probe_bw c3order: what a decode order and a store policy can do for a consumer that
+// follows a producer at C3's byte counts (256 MiB X -> 256 MiB M -> 256 MiB R, no arithmetic):
+//   A     producer and consumer forward, non-temporal stores (the codec's defaults)
+//   B     the consumer last-first
+//   C(K)  B, and default-policy stores for the last K MiB the producer writes
+// and the producer-only cost of each store policy (X1 -> M1, X2 -> M2 alternating: nothing is re-read).
+static int c3order() {
+  const size_t sb = 256ull << 20;
+  const int64_t per = (int64_t)(sb / 8 / 8);  // u32x2 elements per stream
+  void *x, *m, *r, *m2;
+  if (hipMalloc(&x, sb) || hipMalloc(&m, sb) || hipMalloc(&r, sb) || hipMalloc(&m2, sb)) return 1;
+  hipMemset(x, 1, sb);
+  hipMemset(m, 2, sb);
+  hipMemset(r, 3, sb);
+  hipMemset(m2, 4, sb);
+  const int reps = 20;
+  hipEvent_t ev[2 * reps + 1];
+  for (auto& e : ev) hipEventCreate(&e);
+  auto enc = [&](const void* src, void* dst, int stc_from) {
+    split8t<<<kOrderBlocks, 256>>>((const u32x4*)src, (u32x2*)dst, per, 0, stc_from);
+  };
+  auto dec = [&](int rev) { merge8t<<<kOrderBlocks, 256>>>((const u32x2*)m, (u32x4*)r, per, rev); };
+  // an event between every two launches: the mean time of the even and of the odd launches
+  auto timed = [&](auto even, auto odd, double& te, double& to) {
+    for (int w = 0; w < 3; ++w) {
+      even();
+      odd();
+    }
+    hipEventRecord(ev[0]);
+    for (int i = 0; i < reps; ++i) {
+      even();
+      hipEventRecord(ev[2 * i + 1]);
+      odd();
+      hipEventRecord(ev[2 * i + 2]);
+    }
+    hipEventSynchronize(ev[2 * reps]);
+    te = to = 0;
+    for (int i = 0; i < reps; ++i) {
+      float a, b;
+      hipEventElapsedTime(&a, ev[2 * i], ev[2 * i + 1]);
+      hipEventElapsedTime(&b, ev[2 * i + 1], ev[2 * i + 2]);
+      te += a * 1e3 / reps;
+      to += b * 1e3 / reps;
+    }
+  };
+  const int tails[] = {0, 32, 64, 96, 128, 192, 256};  // MiB of the producer's output stored cached
+  for (int round = 0; round < 3; ++round) {
+    for (int rev : {0, 1})
+      for (int K : tails) {
+        if (!rev && K) continue;
+        const int from = kOrderBlocks - K * 32;  // a block writes 32 KiB
+        double te, td;
+        timed([&] { enc(x, m, from); }, [&] { dec(rev); }, te, td);
+        printf("c3order round=%d pair     %s K=%-3d  enc %6.1f  dec %6.1f  pair %6.1f us\n", round,
+               rev ? (K ? "C" : "B") : "A", K, te, td, te + td);
+      }
+    for (int K : tails) {
+      const int from = kOrderBlocks - K * 32;
+      double t1, t2;
+      timed([&] { enc(x, m, from); }, [&] { enc(r, m2, from); }, t1, t2);
+      printf("c3order round=%d producer %s K=%-3d  enc %6.1f us (mean of X1->M1 %6.1f, X2->M2 %6.1f)\n", round,
+             K ? "C" : "A=B", K, 0.5 * (t1 + t2), t1, t2);
+    }
+  }
+  return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "c3order")) return c3order();
   if (argc > 1 && argv[1][0] == 'c') {  // C2- (64 MiB) or C3-sized (256 MiB: "c3") ceilings
     const bool c3 = argv[1][1] == '3';
     const size_t sb = (c3 ? 256ull : 64ull) << 20;
