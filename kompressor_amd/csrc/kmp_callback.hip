@@ -26,13 +26,6 @@
 namespace kmp {
 namespace cb {
 
-constexpr int kThreads = 256;
-
-static inline unsigned grid_for(int64_t n) {
-  int64_t g = ceil_div(n, kThreads);
-  return (unsigned)(g > 65536 ? 65536 : (g < 1 ? 1 : g));
-}
-
 // window[b, j, c] = src[b, mult * sym(sym(j - p, L), E), c] per spatial axis (mult 2: highres,
 // 1: trimmed lowres); W = L + 2p, unused leading axis has extent 1.
 template <typename T>
@@ -54,14 +47,6 @@ __global__ void __launch_bounds__(kThreads) window_kernel(const T* __restrict__ 
 // Row form (C == 1, < 2^30 elements): item = 16 B of one window row; the row's source row is
 // resolved once, interior chunks are one 16-byte copy (lowres source) or two 16-byte loads whose
 // even elements are kept (highres source), edge chunks mirror per element.
-__device__ __forceinline__ int32_t sym32(int32_t i, int32_t n) {
-  if (i >= 0 && i < n) return i;
-  if (i >= -n && i < 2 * n) return i < 0 ? -1 - i : 2 * n - 1 - i;
-  int32_t m = i % (2 * n);
-  if (m < 0) m += 2 * n;
-  return m < n ? m : 2 * n - 1 - m;
-}
-
 template <typename T>
 __global__ void __launch_bounds__(kThreads) rows_window_kernel(const T* __restrict__ src, int32_t S0, int32_t S1,
                                                              int32_t S2, Geo g, int mult, int pz, int p, int32_t W0,
@@ -72,7 +57,8 @@ __global__ void __launch_bounds__(kThreads) rows_window_kernel(const T* __restri
   const int32_t E0 = (int32_t)g.E[0], E1 = (int32_t)g.E[1], E2 = (int32_t)g.E[2];
   for (int32_t t = blockIdx.x * kThreads + threadIdx.x; t < items; t += gridDim.x * kThreads) {
     const RowItem q = row_item((uint32_t)t, W0, W1, nch);
-    const int32_t z = mult * sym32(sym32(q.z - pz, L0), E0), y = mult * sym32(sym32(q.y - p, L1), E1);
+    const int32_t z = mult * sym_idx<int32_t>(sym_idx<int32_t>(q.z - pz, L0), E0);
+    const int32_t y = mult * sym_idx<int32_t>(sym_idx<int32_t>(q.y - p, L1), E1);
     const T* row = src + ((q.b * S0 + z) * S1 + y) * S2;
     T* dst = out + ((q.b * W0 + q.z) * W1 + q.y) * W2;
     const int32_t x0 = q.j * V, xs = x0 - p;
@@ -92,7 +78,7 @@ __global__ void __launch_bounds__(kThreads) rows_window_kernel(const T* __restri
       }
       o.store(dst + x0);
     } else {
-      for (int32_t x = x0; x < x0 + V && x < W2; ++x) dst[x] = row[mult * sym32(sym32(x - p, L2), E2)];
+      for (int32_t x = x0; x < x0 + V && x < W2; ++x) dst[x] = row[mult * sym_idx<int32_t>(sym_idx<int32_t>(x - p, L2), E2)];
     }
   }
 }
@@ -600,17 +586,17 @@ int kmp_encode_with_predictions_typed(int32_t nsp, int32_t dtype, int32_t coder,
       const cb::MapExt me = cb::map_exts(g, nsp);
       const int64_t nch = ceil_div(g.E[2], Vec16<T>::V), items = B * g.E[0] * g.E[1] * nch;
       auto k = nsp == 3 ? cb::rows_code_preds_kernel<T, CODER, false, 3, P> : cb::rows_code_preds_kernel<T, CODER, false, 2, P>;
-      k<<<cb::grid_for(items), cb::kThreads, 0, (hipStream_t)stream>>>(
+      k<<<grid_for(items), kThreads, 0, (hipStream_t)stream>>>(
           (const T*)highres, CMapPtrs{}, mp, pp, (T*)lowres_out, me, (int32_t)g.n[0], (int32_t)g.n[1],
           (int32_t)g.n[2], (int32_t)g.E[0], (int32_t)g.E[1], (int32_t)g.E[2], (int32_t)nch, (int32_t)items);
     } else if (small) {
       const cb::MapExt me = cb::map_exts(g, nsp);
       auto k = nsp == 3 ? cb::code_preds_kernel32<T, CODER, false, 7, P> : cb::code_preds_kernel32<T, CODER, false, 3, P>;
-      k<<<cb::grid_for(total), cb::kThreads, 0, (hipStream_t)stream>>>(
+      k<<<grid_for(total), kThreads, 0, (hipStream_t)stream>>>(
           (const T*)highres, CMapPtrs{}, mp, pp, (T*)lowres_out, me, (int32_t)g.n[0], (int32_t)g.n[1],
           (int32_t)g.n[2], (int32_t)g.E[0], (int32_t)g.E[1], (int32_t)g.E[2], (int32_t)total);
     } else {
-      cb::encode_preds_kernel<T, CODER, P><<<cb::grid_for(total), cb::kThreads, 0, (hipStream_t)stream>>>(
+      cb::encode_preds_kernel<T, CODER, P><<<grid_for(total), kThreads, 0, (hipStream_t)stream>>>(
           (const T*)highres, g, nsp, C, pp, (T*)lowres_out, mp, total);
     }
     return check_launch("encode_with_predictions");
@@ -656,17 +642,17 @@ int kmp_decode_with_predictions_typed(int32_t nsp, int32_t dtype, int32_t coder,
       const cb::MapExt me = cb::map_exts(g, nsp);
       const int64_t nch = ceil_div(g.E[2], Vec16<T>::V), items = B * g.E[0] * g.E[1] * nch;
       auto k = nsp == 3 ? cb::rows_code_preds_kernel<T, CODER, true, 3, P> : cb::rows_code_preds_kernel<T, CODER, true, 2, P>;
-      k<<<cb::grid_for(items), cb::kThreads, 0, (hipStream_t)stream>>>(
+      k<<<grid_for(items), kThreads, 0, (hipStream_t)stream>>>(
           (const T*)lowres, mp, MapPtrs{}, pp, (T*)highres_out, me, (int32_t)g.n[0], (int32_t)g.n[1],
           (int32_t)g.n[2], (int32_t)g.E[0], (int32_t)g.E[1], (int32_t)g.E[2], (int32_t)nch, (int32_t)items);
     } else if (small) {
       const cb::MapExt me = cb::map_exts(g, nsp);
       auto k = nsp == 3 ? cb::code_preds_kernel32<T, CODER, true, 7, P> : cb::code_preds_kernel32<T, CODER, true, 3, P>;
-      k<<<cb::grid_for(total), cb::kThreads, 0, (hipStream_t)stream>>>(
+      k<<<grid_for(total), kThreads, 0, (hipStream_t)stream>>>(
           (const T*)lowres, mp, MapPtrs{}, pp, (T*)highres_out, me, (int32_t)g.n[0], (int32_t)g.n[1],
           (int32_t)g.n[2], (int32_t)g.E[0], (int32_t)g.E[1], (int32_t)g.E[2], (int32_t)total);
     } else {
-      cb::decode_preds_kernel<T, CODER, P><<<cb::grid_for(total), cb::kThreads, 0, (hipStream_t)stream>>>(
+      cb::decode_preds_kernel<T, CODER, P><<<grid_for(total), kThreads, 0, (hipStream_t)stream>>>(
           (const T*)lowres, mp, g, nsp, C, pp, (T*)highres_out, total);
     }
     return check_launch("decode_with_predictions");

@@ -1,5 +1,5 @@
 // kmp_codec.h -- internal interfaces between the fused-codec translation units: the request every
-// one-pass kernel family takes, one entry point per family, and the host checks they share.
+// kernel family takes, one entry point per family, and the host checks they share.
 #pragma once
 
 #include "kmp_aggregate.h"
@@ -37,10 +37,19 @@ struct CodecCall {
   hipStream_t stream;
 };
 
-// One-pass kernel families, one per kmp_codec_<family>.hip.  Each returns KMP_ERR_UNSUPPORTED
-// (without touching anything) when the request is not eligible, and knows nothing of the others:
-// the order they are tried in is the table next to codec_encode / codec_decode
-// (kmp_codec_generic.hip).  Instantiated for uint8_t / uint16_t, wave3d32 for int32_t / uint32_t.
+// The coder of a request is the natural coder of its sample type (the front door admits no other
+// pair): (u8, U8), (u16, U16), (i32, RAW), (u32, U32).
+template <typename T> struct natural_coder;
+template <> struct natural_coder<uint8_t> { static constexpr int value = KMP_CODER_U8; };
+template <> struct natural_coder<uint16_t> { static constexpr int value = KMP_CODER_U16; };
+template <> struct natural_coder<int32_t> { static constexpr int value = KMP_CODER_RAW; };
+template <> struct natural_coder<uint32_t> { static constexpr int value = KMP_CODER_U32; };
+
+// Kernel families, one per kmp_codec_<family>.hip.  Each returns KMP_ERR_UNSUPPORTED (without
+// touching anything) when the request is not eligible, and knows nothing of the others: the order
+// they are tried in is the table next to codec_encode / codec_decode (kmp_codec.hip).  The one-pass
+// families are instantiated for uint8_t / uint16_t, wave3d32 for int32_t / uint32_t; the generic
+// two-pass path for all four, and it takes every request.
 template <typename T, bool DEC> int try_wave3d(const CodecCall<T, DEC>& c);
 template <typename T, bool DEC> int try_wave3d32(const CodecCall<T, DEC>& c);
 template <typename T, bool DEC> int try_wave3dp(const CodecCall<T, DEC>& c);
@@ -52,11 +61,13 @@ template <typename T, bool DEC> int try_linear3pm(const CodecCall<T, DEC>& c);
 template <typename T, bool DEC> int try_wave2d(const CodecCall<T, DEC>& c);
 template <typename T, bool DEC> int try_wave2dp(const CodecCall<T, DEC>& c);
 template <typename T, bool DEC> int try_fast2d(const CodecCall<T, DEC>& c);
+template <typename T, bool DEC> int try_generic(const CodecCall<T, DEC>& c);
 
 #define KMP_INST_FAMILY(F, T)                           \
   template int F<T, false>(const CodecCall<T, false>&); \
   template int F<T, true>(const CodecCall<T, true>&);
 #define KMP_INST_FAMILY_U8_U16(F) KMP_INST_FAMILY(F, uint8_t) KMP_INST_FAMILY(F, uint16_t)
+#define KMP_FOR_SAMPLE_TYPES(M) M(uint8_t) M(uint16_t) M(int32_t) M(uint32_t)
 
 // ------------------------------------------------------------------------------------------
 // Host checks and argument filling the families share

@@ -153,6 +153,14 @@ __host__ __device__ __forceinline__ int64_t sym_index(int64_t i, int64_t n) {
   if (m < 0) m += 2 * n;
   return m < n ? m : 2 * n - 1 - m;
 }
+template <typename I>
+__device__ __forceinline__ I sym_idx(I i, I n) {  // sym_index in the kernel's index type
+  if (i >= 0 && i < n) return i;
+  if (i >= -n && i < 2 * n) return i < 0 ? -1 - i : 2 * n - 1 - i;
+  I m = i % (2 * n);
+  if (m < 0) m += 2 * n;
+  return m < n ? m : 2 * n - 1 - m;
+}
 
 // ------------------------------------------------------------------------------------------
 // Geometry of the reference's single pyramid level (volume/utils.py:226-237, 263-276)
@@ -225,6 +233,13 @@ struct CMapPtrs {
 };
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// the grid-stride kernels' block size, and their grid for n work items
+constexpr int kThreads = 256;
+inline unsigned grid_for(int64_t n) {
+  const int64_t g = ceil_div(n, kThreads);
+  return (unsigned)(g > 65536 ? 65536 : (g < 1 ? 1 : g));
+}
 
 // n / d for a wave-uniform 0 <= n < 2^31 and a launch-constant d >= 1 as q = mulhi(n, m) >> s (s < 0:
 // d == 1, q = n), m = floor(2^(31+l) / d) + 1 with l = ceil(log2 d): exact on 31-bit n (error m d - 2^(31+l)

@@ -26,15 +26,6 @@ int check_launch(const char* what) {
   return KMP_OK;
 }
 
-constexpr int kThreads = 256;
-
-static inline unsigned grid_for(int64_t n) {
-  int64_t g = ceil_div(n, kThreads);
-  if (g > 65536) g = 65536;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
 // Every kernel below is instantiated with a 32-bit index type when all the arrays it touches
 // have fewer than 2^30 elements (64-bit multiplies and divisions are multi-instruction sequences
 // on gfx950), and with I otherwise.
@@ -62,14 +53,6 @@ __device__ __forceinline__ IdxT<I> unflat_t(I t, I e0, I e1, I e2, I C) {
     unflat5(t, e0, e1, e2, C, r.b, r.i0, r.i1, r.i2, r.c);
   }
   return r;
-}
-template <typename I>
-__device__ __forceinline__ I sym_idx(I i, I n) {  // sym_index in the kernel's index type
-  if (i >= 0 && i < n) return i;
-  if (i >= -n && i < 2 * n) return i < 0 ? -1 - i : 2 * n - 1 - i;
-  I m = i % (2 * n);
-  if (m < 0) m += 2 * n;
-  return m < n ? m : 2 * n - 1 - m;
 }
 
 // ------------------------------------------------------------------------------------------

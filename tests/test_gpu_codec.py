@@ -748,7 +748,7 @@ def test_encode_store_policy_is_output_neutral(kom, case, cached, kmp_opt):
     (2, (2, 61, 77, 3), np.uint8, 2, None),        # RGB
 ])
 def test_generic_mean_cells_match_oracle(kom, ndim, shape, dtype, p, top):
-    """The generic path's cell means (kmp_codec_generic.hip cell_mean_row_kernel: 4 cells of a row
+    """The generic path's cell means (kmp_codec_generic_cells.hip cell_mean_row_kernel: 4 cells of a row
     per thread, exact integer sums or the reference's in-order float sum) on shapes the one-pass
     kernels do not take, paddings up to 3, against the oracle, encode and decode."""
     import oracle
@@ -766,3 +766,40 @@ def test_generic_mean_cells_match_oracle(kom, ndim, shape, dtype, p, top):
         bad = np.argwhere(a != b)
         assert bad.size == 0, f'map {i}: {len(bad)} mismatches, first at {bad[:3].tolist()}'
     assert np.array_equal(ns.decode(pred, dec, lo, (maps, dims), padding=p), x)
+
+
+@pytest.mark.parametrize('ndim,shape,dtype,kind,p', [
+    (3, (1, 5, 6, 7, 3), np.uint16, 'linear', 0),  # per-element kernel, a value per map channel, 32-bit indices
+    (3, (1, 5, 6, 7, 3), np.uint8, 'mean', 1),     # per-element kernel, one value per cell
+    (2, (2, 9, 11, 4), np.uint8, 'mean', 1),       # row kernel at 4 channels, a partial last group of columns
+])
+def test_generic_residual_kernels_match_oracle(kom, kmp_opt, ndim, shape, dtype, kind, p):
+    """The generic path's residual pass on whole arrays, one-pass kernels off: the per-element kernel
+    (kmp_codec_generic.hip, one kernel for encode and decode; volumes with 3 channels) and the row
+    kernel at its widest channel count (kmp_codec_generic_row4.hip), bit-exact against the oracle,
+    encode and decode.  (Their 64-bit-index instances need arrays of 2^31 elements: not run here.)"""
+    import oracle
+    from oracle import predictors as OP
+    kmp_opt('KMP_DISABLE_FAST', 1)
+    ns, ons = (kom.volume, oracle.volume) if ndim == 3 else (kom.image, oracle.image)
+    enc, dec, oenc = (ns.encode_values_uint16, ns.decode_values_uint16, ons.encode_values_uint16) \
+        if dtype == np.uint16 else (ns.encode_values_uint8, ns.decode_values_uint8, ons.encode_values_uint8)
+    rng = np.random.default_rng(33)
+    x = rng.integers(0, np.iinfo(dtype).max + 1, size=shape, dtype=np.int64).astype(dtype)
+    if kind == 'linear':
+        n, k = (2 * p + 2) ** ndim, 19 if ndim == 3 else 5
+        w = (1.0 / n + rng.standard_normal((n, k)) * (0.3 / n)).astype(np.float32)  # ~ a noisy mean
+        b = (rng.standard_normal(k) * 50.0).astype(np.float32)
+        pred, opred = kom.LinearPredictor(w, b, p, ndim, arith='f32'), OP.linear_predictions_fn(p, w, b, ndim)
+    else:
+        pred, opred = kom.MeanPredictor(p, ndim), OP.mean_predictions_fn(p, ndim)
+    want_lo, (want_maps, want_dims) = ons.encode(opred, oenc, x, padding=p)
+    lo, (maps, dims) = ns.encode(pred, enc, x, padding=p)
+    assert _last_launch(kom) == 'encode_generic'
+    assert tuple(dims) == tuple(want_dims) and np.array_equal(lo, want_lo)
+    for i, (a, b_) in enumerate(zip(maps, want_maps)):
+        bad = np.argwhere(a != b_)
+        assert bad.size == 0, f'map {i}: {len(bad)} mismatches, first at {bad[:3].tolist()}'
+    rec = ns.decode(pred, dec, want_lo, (want_maps, want_dims), padding=p)
+    assert _last_launch(kom) == 'decode_generic'
+    assert np.array_equal(rec, x)

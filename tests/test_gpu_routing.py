@@ -2,7 +2,7 @@
 
 Each row is a configuration with the launch names ``kmp_last_launch()`` reports after its encode and
 its decode.  The expected names are literals recorded from the library as it was before the
-dispatch moved into one table (kmp_codec_generic.hip), so a reordered or dropped table entry shows
+dispatch moved into one table (kmp_codec.hip), so a reordered or dropped table entry shows
 up here as a changed name.  Every row also checks that one family serves both directions and that
 the round trip is lossless."""
 
