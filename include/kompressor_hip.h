@@ -381,6 +381,37 @@ int kmp_rice_bundle_decode_ranges(int32_t dtype, const kmp_rice_range* ranges, i
 /* ``data`` 16-byte aligned.  One memset of *crc_out + one launch.                               */
 int kmp_crc32(const uint8_t* data, int64_t n_max, const int64_t* n_dev, uint32_t* crc_out, kmp_stream_t stream);
 
+/* Per-tile CRC-32 of a v2 Rice bundle (kmp_crc.hip; no reference counterpart, as above): the      */
+/* checksum at the granularity a partial read touches.  For tile t of an array of n samples, with  */
+/* nbk = min(256, ceil(n / 64) - 256 t) blocks and payload words [toff[t], closing):               */
+/*   tile_crc = zlib.crc32(params[256 t : 256 t + nbk] || bw[256 t : 256 t + nbk] || the payload   */
+/*              words as little-endian bytes)                                                      */
+/* (a tile without payload words: the CRC of its 2 nbk side bytes).  One record covers tiles       */
+/* t0 .. t1 of one array; as in kmp_rice_range every piece is a device pointer of its own, into a  */
+/* resident bundle or at a WINDOW read from a file:                                                */
+typedef struct kmp_rice_crc_range {
+  int64_t n;               /* samples of the whole array (fixes the last tile's block count)      */
+  int64_t t0, t1;          /* 0 <= t0 <= t1 < kmp_rice_tiles(n)                                    */
+  const uint8_t* params;   /* params / bw from block 256 * t0 on, up to block                     */
+  const uint8_t* bw;       /* min(ceil(n / 64), 256 * (t1 + 1)) - 1                               */
+  const uint64_t* toff;    /* 8-aligned: the word offsets of tiles t0 .. t1 (t1 - t0 + 1 entries) */
+  const uint64_t* closing; /* 8-aligned: the word tile t1 ends at -- the next table entry, or the */
+                           /* end-word field of the array's record inside the bundle (so a fresh  */
+                           /* encode is checksummed without a copy or a host round trip)          */
+  const uint32_t* payload; /* 4-aligned: the payload from word ``payload_first`` on               */
+  uint64_t payload_first;  /* the payload word payload[0] holds                                    */
+  uint64_t payload_words;  /* words readable at ``payload``                                        */
+  uint32_t* crc_out;       /* write mode: crc_out[t - t0] = tile_crc(t); no other byte is written */
+  const uint32_t* expect;  /* check mode (crc_out null): every tile whose CRC differs from        */
+                           /* expect[t - t0] adds 1 to *bad                                        */
+} kmp_rice_crc_range;
+/* One launch for ``count`` (<= 32) records of any dtypes; a wave checksums one tile at a time and */
+/* a workgroup walks several.  A tile whose span lies outside [payload_first, payload_first +     */
+/* payload_words), runs backwards or exceeds 256 * (2 * 32 + 2) words is unusable: nothing is     */
+/* read from it, it adds 1 to *bad (caller-zeroed device uint64; may be null in write mode) and   */
+/* write mode stores 0.  No allocation, no synchronisation; graph-capturable.                     */
+int kmp_rice_tile_crc(const kmp_rice_crc_range* ranges, int32_t count, unsigned long long* bad, kmp_stream_t stream);
+
 /* Bit-plane side-information check (the planes format): count the blocks whose stored widths   */
 /* no encoder produces (> W) -- format 0 -- or, format 1, Rice params / bw -- into the uint64 at  */
 /* workspace + kmp_pack_total_offset(n) + 8, beside the payload length of the last scan          */

@@ -60,6 +60,13 @@ class RiceRange(ctypes.Structure):  # kmp_rice_range (include/kompressor_hip.h)
                 ('payload_words', ctypes.c_uint64)]
 
 
+class RiceCrcRange(ctypes.Structure):  # kmp_rice_crc_range (include/kompressor_hip.h)
+    _fields_ = [('n', ctypes.c_int64), ('t0', ctypes.c_int64), ('t1', ctypes.c_int64), ('params', ctypes.c_void_p),
+                ('bw', ctypes.c_void_p), ('toff', ctypes.c_void_p), ('closing', ctypes.c_void_p),
+                ('payload', ctypes.c_void_p), ('payload_first', ctypes.c_uint64), ('payload_words', ctypes.c_uint64),
+                ('crc_out', ctypes.c_void_p), ('expect', ctypes.c_void_p)]
+
+
 class Region(ctypes.Structure):
     _fields_ = [('begin', ctypes.c_int64 * 3), ('end', ctypes.c_int64 * 3)]
 
@@ -122,6 +129,7 @@ _PROTOS = {
     'kmp_rice_bundle_decode': (ctypes.c_int, [_i32, _vp, _i32, _i64, _vp, _i64, ctypes.c_uint64, _vp, _vp]),
     'kmp_rice_bundle_decode_ranges': (ctypes.c_int, [_i32, _vp, _i32, _vp, _vp]),
     'kmp_crc32': (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    'kmp_rice_tile_crc': (ctypes.c_int, [_vp, _i32, _vp, _vp]),
     'kmp_decode_with_predictions': (ctypes.c_int, [_i32, _i32, _i32, _vp, _vpp, _i64, _i64p, _i64, _i32p, _vpp,
                                                    _vp, _vp]),
     'kmp_encode_with_predictions_typed': (ctypes.c_int, [_i32, _i32, _i32, _i32, _vp, _i64, _i64p, _i64, _vpp, _vp,

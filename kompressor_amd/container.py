@@ -15,7 +15,12 @@ sample dtype (float32 volumes travel bit-cast to uint32) and a CRC-32 of the pay
     lowres, encoded, meta = load(path)
 
 File layout (little-endian): ``b'KMPF' u16 version u16 0 u64 meta_len``, the metadata as UTF-8
-JSON padded to 8 bytes, then the ``pack_encoded`` bundle (``meta['bundle_bytes']`` bytes).
+JSON padded to 8 bytes, then the ``pack_encoded`` bundle (``meta['bundle_bytes']`` bytes).  A file
+written with ``tile_crc=True`` continues with zero bytes to an 8-byte boundary and a u32 table of
+one CRC-32 per bundle tile (``meta['tile_crc'] = {'offset', 'tiles'}``, the offset from the bundle's
+start; ``packing.tile_crcs``): ``read_region`` verifies the tiles it touches against it, ``check``
+and a failing ``decompress`` name the damaged ones.  ``bundle_bytes`` and ``crc32`` cover the bundle
+alone either way, and a reader that does not know the key reads the file as before.
 
 The host side of the file path (round 4): the bundle's CRC-32 (zlib's, the value the file stores)
 is computed on the device (``kmp_crc32``) -- over the bundle the encode just wrote, its length read
@@ -36,7 +41,7 @@ import torch
 
 from . import _device as dev
 from . import _nd, packing
-from ._lib import check, lib
+from ._lib import check as _check, lib
 from .predictors import ARITH_REV, LinearPredictor, MeanPredictor
 
 # wall-time split (seconds) of the last compress / decompress / save / load of this process
@@ -98,60 +103,79 @@ def _device_crc(blob, n_max, n_dev=None):
     """zlib CRC-32 of the device bytes ``blob[:n]`` (n = ``n_max``, or the device int64 at ``n_dev``
     capped to ``n_max``) as a 1-element device uint32 tensor; no synchronisation."""
     out = torch.empty((1,), dtype=torch.int32, device='cuda')
-    check(lib.kmp_crc32(blob.data_ptr(), int(n_max), n_dev, out.data_ptr(), dev.stream()), 'crc32')
+    _check(lib.kmp_crc32(blob.data_ptr(), int(n_max), n_dev, out.data_ptr(), dev.stream()), 'crc32')
     return out
 
 
-def _bundle(x, arrays, dims, method):
-    """Entropy-code an encode result on the device: ``(device bytes, bundle length, crc32)`` with ONE
-    synchronisation (length and CRC read back together)."""
+def _bundle(x, arrays, dims, method, tile_crc=False):
+    """Entropy-code an encode result on the device: ``(device bytes, bundle length, crc32, per-tile
+    CRC table bytes or None)`` with ONE synchronisation (length, CRC and -- ``tile_crc`` -- the table,
+    computed by ``kmp_rice_tile_crc`` on the same stream right after the encode, read back together)."""
     if method == 'rice':
         out, poff, launched, keep = packing._rice_encode_launch((x, *arrays), dims)
+        T = 0
+        if tile_crc and launched:
+            plan = packing._rice_enc_plan(keep, dims)
+            T = plan['T']
+            table = torch.empty((T,), dtype=torch.int32, device='cuda')
+            # the payload's extent is not known on the host yet: the spans are checked against the buffer
+            packing._launch_tile_crc(packing._resident_crc_records(
+                out.data_ptr(), plan['ns'], plan['offs'], poff, (out.numel() - poff) // 4, table.data_ptr()), None)
+        head = dev.pinned_staging(64 + 4 * T, 'head')
         if not launched:  # no samples: the header and side arrays only
             total = poff
             crc = _device_crc(out, total)
-            head = dev.pinned_staging(64, 'head')
             head[:4].copy_(crc.view(torch.uint8), non_blocking=True)
         else:
             crc = _device_crc(out, out.numel(), out[64:72].data_ptr())  # the size field of the header
-            head = dev.pinned_staging(64, 'head')
             head[:16].copy_(out[56:72], non_blocking=True)
             head[16:20].copy_(crc.view(torch.uint8), non_blocking=True)
+            if T:
+                head[64:64 + 4 * T].copy_(table.view(torch.uint8), non_blocking=True)
         torch.cuda.current_stream().synchronize()
         hb = head[:20].numpy().tobytes()
+        tab = head[64:64 + 4 * T].numpy().tobytes() if tile_crc else None
         del keep
         if launched:
             _, total = struct.unpack('<2q', hb[:16])
-            return out, int(total), struct.unpack('<I', hb[16:20])[0]
-        return out, int(total), struct.unpack('<I', hb[:4])[0]
+            return out, int(total), struct.unpack('<I', hb[16:20])[0], tab
+        return out, int(total), struct.unpack('<I', hb[:4])[0], tab
+    if tile_crc:
+        raise ValueError("tile_crc=True needs method='rice' (a 'planes' bundle has no tiles)")
     blob = packing.pack_encoded(x, (arrays, dims), method)
     crc = _device_crc(blob, blob.numel())
-    return blob, blob.numel(), int(crc.cpu().view(torch.uint32).item())
+    return blob, blob.numel(), int(crc.cpu().view(torch.uint32).item()), None
 
 
-def _write(path, meta, blob, total, crc, t0):
+def _write(path, meta, blob, total, crc, t0, table=None):
     """Header, metadata and the first ``total`` device bytes of ``blob`` to ``path``: the bundle
     crosses the link in pinned chunks (``_device.d2h_stream``), each written to the file while the
-    next ones are in flight."""
+    next ones are in flight.  ``table`` (the per-tile CRCs, u32 little-endian) follows the bundle,
+    8-aligned, and is recorded in the metadata as ``'tile_crc': {'offset', 'tiles'}``."""
     t1 = time.perf_counter()
     meta = dict(meta, bundle_bytes=int(total), crc32=int(crc) & 0xffffffff)
+    trailer = b''
+    if table is not None:
+        meta['tile_crc'] = {'offset': int(total) + (-int(total) % 8), 'tiles': len(table) // 4}
+        trailer = b'\0' * (-int(total) % 8) + table
     js = json.dumps(meta, separators=(',', ':')).encode()
     js += b' ' * (-len(js) % 8)
     tmp = f'{path}.tmp{os.getpid()}'
     with open(tmp, 'wb') as f:
         try:  # the file's blocks allocated up front: the write then only copies (8.0 vs 10.0 ms for
-            os.posix_fallocate(f.fileno(), 0, _HEAD.size + len(js) + total)  # 112 MB, write_probe_r5w2.log)
+            os.posix_fallocate(f.fileno(), 0, _HEAD.size + len(js) + total + len(trailer))  # 112 MB, write_probe_r5w2.log)
         except OSError:
             pass  # a filesystem without fallocate: the writes allocate
         f.write(_HEAD.pack(MAGIC, VERSION, 0, len(js)))
         f.write(js)
         if total:
             dev.d2h_stream(blob[:total], lambda lo, piece: f.write(memoryview(piece)))
+        f.write(trailer)
     os.replace(tmp, path)  # a reader never sees a half-written file
     t2 = time.perf_counter()
     last_timing.clear()
     last_timing.update(device=t1 - t0, d2h_write=t2 - t1, total=t2 - t0)
-    return _HEAD.size + len(js) + total
+    return _HEAD.size + len(js) + total + len(trailer)
 
 
 def _builtin_padding(predictor, padding):
@@ -164,15 +188,24 @@ def _builtin_padding(predictor, padding):
     return 0 if padding is None else int(padding)
 
 
-def save(path, lowres, encoded, predictor=None, padding=None, ndim=None, method='rice', sample_dtype=None):
+def _check_tile_crc_method(tile_crc, method):
+    if tile_crc and method != 'rice':
+        raise ValueError("tile_crc=True needs method='rice' (a 'planes' bundle has no tiles)")
+
+
+def save(path, lowres, encoded, predictor=None, padding=None, ndim=None, method='rice', sample_dtype=None,
+         tile_crc=False):
     """Write an ``encode`` result ``(lowres, (maps, dims))`` to ``path``; returns the file size.
     ``predictor`` is recorded so :func:`decompress` can decode without being told.  ``padding``
-    defaults to a built-in predictor's own padding (0 for an external predictions_fn)."""
+    defaults to a built-in predictor's own padding (0 for an external predictions_fn).
+    ``tile_crc=True`` (``method='rice'``) appends the per-tile CRC table :func:`read_region` checks
+    the tiles it touches against."""
     maps, dims = encoded
     ndim = ndim or len(dims)
     padding = _builtin_padding(predictor, padding)
     t0 = time.perf_counter()
     packing._check_method(method)
+    _check_tile_crc_method(tile_crc, method)
     lo_t = dev.to_device(lowres)[0]
     maps_t = [dev.to_device(m)[0] for m in maps]
     meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'dims': [int(d) for d in dims],
@@ -180,8 +213,8 @@ def save(path, lowres, encoded, predictor=None, padding=None, ndim=None, method=
             'map_dtype': _NP_NAME[maps_t[0].dtype],
             'sample_dtype': sample_dtype or _NP_NAME[lo_t.dtype],
             'predictor': _predictor_meta(predictor, padding, ndim, lo_t.dtype) if predictor is not None else None}
-    blob, total, crc = _bundle(lo_t, maps_t, dims, method)
-    return _write(path, meta, blob, total, crc, t0)
+    blob, total, crc, table = _bundle(lo_t, maps_t, dims, method, tile_crc)
+    return _write(path, meta, blob, total, crc, t0, table)
 
 
 def _read_head(f, path):
@@ -227,19 +260,75 @@ def _read(path):
     return meta, blob, crc, {'read_upload': t1 - t0, 't_upload': t1}
 
 
-def _check_crc(path, meta, crc):
+def _check_crc(path, meta, crc, blob=None):
     """The device CRC against the file's (one small read-back; the caller's own synchronisation
-    usually has already drained the stream)."""
+    usually has already drained the stream).  On a mismatch of a file that has a per-tile CRC table,
+    ``blob`` (the resident bundle) is checked tile by tile and the message names the damaged
+    ``(array, tile)`` pairs."""
     got = int(crc.cpu().view(torch.uint32).item()) if meta['bundle_bytes'] else 0
     if got != (int(meta['crc32']) & 0xffffffff):
-        raise ValueError(f'{path}: payload CRC mismatch (corrupt file)')
+        where = ''
+        if blob is not None and meta.get('tile_crc') is not None:
+            try:
+                T, bad = _damaged_tiles(path, meta, blob)
+                shown = ', '.join(f'({a}, {t})' for a, t in bad[:8])
+                where = f': {len(bad)} of {T} tiles damaged, (array, tile) = {shown}{", ..." if len(bad) > 8 else ""}' \
+                    if bad else f': all {T} tile CRCs match, the damage lies outside the tiles'
+            except ValueError as e:  # the table or the bundle's layout is itself unusable
+                where = f'; the per-tile CRC table could not be used ({e})'
+        raise ValueError(f'{path}: payload CRC mismatch (corrupt file){where}')
+
+
+def _damaged_tiles(path, meta, blob):
+    """``(T, [(array, tile), ...])``: the tiles of the resident bundle ``blob`` whose CRC differs from
+    the file's per-tile table (``kmp_rice_tile_crc`` over the whole bundle, one launch per 32 arrays,
+    one read-back).  ValueError when the table or the bundle's layout cannot be used."""
+    with open(path, 'rb') as f:
+        _, _, mlen, n = _read_head(f, path)
+        base = _HEAD.size + mlen
+        off, T = _tile_crc_trailer(meta, n, os.fstat(f.fileno()).st_size - base, path)
+        want = np.frombuffer(os.pread(f.fileno(), 4 * T, base + off), np.uint32)
+    if want.size != T:
+        raise ValueError(f'{path}: truncated per-tile CRC table')
+    got = packing.tile_crcs(blob)
+    if got.numel() != T:
+        raise ValueError(f'{path}: the bundle holds {got.numel()} tiles, the per-tile CRC table {T}')
+    got = got.view(torch.int32).cpu().numpy().view(np.uint32)
+    _, _, plan = packing._resident_bundle(blob)
+    begins = _tile_begins([_tiles(k) for k in plan['ns']])
+    bad = []
+    for g in np.flatnonzero(got != want):
+        a = max(i for i, b in enumerate(begins) if b <= g)
+        bad.append((int(a), int(g - begins[a])))
+    return T, bad
+
+
+def check(path):
+    """Verify a file without decoding it: ``{'ok', 'crc32': whether the bundle's CRC-32 matches,
+    'tile_crc': None for a file without a per-tile table, else {'tiles': T, 'bad': [(array, tile),
+    ...]}}`` (``'error'`` added there when the table or the bundle's layout cannot be used).  Damage
+    is reported, never raised; only a file whose header cannot be read raises ValueError."""
+    meta, blob, crc, _ = _read(path)
+    got = int(crc.cpu().view(torch.uint32).item()) if meta['bundle_bytes'] else 0
+    crc_ok = got == (int(meta['crc32']) & 0xffffffff)
+    tiles = None
+    if meta.get('tile_crc') is not None:
+        try:
+            T, bad = _damaged_tiles(path, meta, blob)
+            tiles = {'tiles': T, 'bad': bad}
+        except ValueError as e:
+            tc = meta['tile_crc']
+            T = tc.get('tiles') if isinstance(tc, dict) else None
+            tiles = {'tiles': T if isinstance(T, int) else 0, 'bad': [], 'error': str(e)}
+    return {'ok': crc_ok and (tiles is None or (not tiles['bad'] and 'error' not in tiles)), 'crc32': crc_ok,
+            'tile_crc': tiles}
 
 
 def load(path, device=True):
     """``(lowres, (maps, dims), meta)`` from a file written by :func:`save` / :func:`compress`;
     device tensors by default, numpy arrays with ``device=False``."""
     meta, blob, crc, _ = _read(path)
-    _check_crc(path, meta, crc)  # before any header parsing of a possibly corrupt bundle
+    _check_crc(path, meta, crc, blob)  # before any header parsing of a possibly corrupt bundle
     lowres, (maps, dims) = packing.unpack_encoded(blob)
     if not device:
         lowres, maps = dev.to_host(lowres), tuple(dev.to_host(m) for m in maps)
@@ -255,15 +344,18 @@ def _auto_levels(shape, ndim, max_levels=4):
     return max(levels, 1)
 
 
-def compress(path, highres, predictor, levels='auto', method='rice'):
+def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False):
     """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
     :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int32
     raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
     reference's single-level ``encode`` (volume/encode_decode.py:30-56) applied to the previous
     level's lowres, so only the coarsest lowres is stored raw -- entropy-code every array and write
-    ``path``.  Returns ``{'bytes', 'raw_bytes', 'ratio', 'bits_per_sample', 'levels'}``."""
+    ``path``.  Returns ``{'bytes', 'raw_bytes', 'ratio', 'bits_per_sample', 'levels'}``.
+    ``tile_crc=True`` (``method='rice'``) appends one CRC-32 per tile of 16384 samples, computed on the
+    device right after the encode, so :func:`read_region` verifies exactly the tiles it reads."""
     t0 = time.perf_counter()
     packing._check_method(method)
+    _check_tile_crc_method(tile_crc, method)
     ndim, padding = predictor.ndim, predictor.padding
     h, _ = dev.to_device(highres)
     sample = _NP_NAME[h.dtype]
@@ -288,8 +380,8 @@ def compress(path, highres, predictor, levels='auto', method='rice'):
             'predictor': _predictor_meta(predictor, padding, ndim, x.dtype)}
     # one bundle: the coarsest lowres, then every level's maps finest first (no bundle dims: the
     # per-level dims live in the metadata)
-    blob, total, crc = _bundle(x, arrays, (), method)
-    nbytes = _write(path, meta, blob, total, crc, t0)
+    blob, total, crc, table = _bundle(x, arrays, (), method, tile_crc)
+    nbytes = _write(path, meta, blob, total, crc, t0, table)
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
             'levels': levels}
@@ -323,7 +415,7 @@ def decompress(path, predictor=None, as_numpy=True):
     for bit, coarsest level first.  A file coded with an external predictions_fn needs it passed."""
     t0 = time.perf_counter()
     meta, blob, crc, tm = _read(path)
-    _check_crc(path, meta, crc)
+    _check_crc(path, meta, crc, blob)
     t1 = time.perf_counter()
     lowres, (arrays, bundle_dims) = packing.unpack_encoded(blob)
     pred = _decode_predictor(path, meta, predictor, lowres.dtype)
@@ -376,6 +468,7 @@ def _coder_fn(coder, ndim):
 # ---------------------------------------------------------------------------------------------
 
 _TILE = 16384  # samples per tile of a v2 Rice bundle (256 blocks of 64)
+_CRC_TABLE_WHOLE = 256 << 10  # a per-tile CRC table up to this size is read whole when several ranges need entries
 
 
 def info(path):
@@ -389,12 +482,62 @@ def info(path):
     try:
         shapes = _meta_shapes(meta)
         pred = meta.get('predictor') or {}
-        return {'shape': tuple(shapes[0][0]), 'sample_dtype': meta.get('sample_dtype') or meta.get('lowres_dtype'),
-                'ndim': int(meta['ndim']), 'levels': len(shapes), 'padding': int(meta['padding']),
-                'predictor': pred.get('kind'), 'method': meta.get('method'), 'version': version,
-                'file_bytes': int(size), 'bundle_bytes': int(n)}
+        out = {'shape': tuple(shapes[0][0]), 'sample_dtype': meta.get('sample_dtype') or meta.get('lowres_dtype'),
+               'ndim': int(meta['ndim']), 'levels': len(shapes), 'padding': int(meta['padding']),
+               'predictor': pred.get('kind'), 'method': meta.get('method'), 'version': version,
+               'file_bytes': int(size), 'bundle_bytes': int(n)}
+        trailer = _tile_crc_trailer(meta, n, size - (_HEAD.size + mlen), path)
+        if trailer is not None:  # only a file that has a table reports one
+            out['tile_crc'] = trailer[1]
+        return out
     except (KeyError, TypeError, IndexError) as e:
         raise ValueError(f'{path}: corrupt metadata ({e!r})') from None
+
+
+def _meta_tile_counts(meta):
+    """The tile count of every bundle array, in bundle order (the coarsest lowres, then each level's
+    maps, finest level first), from the metadata's shapes alone."""
+    shapes = _meta_shapes(meta)
+    return [_tiles(dev.prod(shapes[-1][1]))] + [_tiles(dev.prod(m)) for _, _, maps, _ in shapes for m in maps]
+
+
+def _tile_begins(counts):
+    """The global table index of every array's first tile: the prefix sum of the tile counts."""
+    out, t = [], 0
+    for c in counts:
+        out.append(t)
+        t += c
+    return out
+
+
+def _tile_crc_trailer(meta, bundle_bytes, avail, path='file'):
+    """``None`` for a file without a per-tile CRC table, else ``(offset from the bundle's start, T)``
+    of its table, checked before anything is sized from it: the table starts at the bundle's end
+    padded to 8 bytes, holds one entry per tile of the shapes the metadata records and lies inside the
+    ``avail`` bytes the file holds after its metadata."""
+    tc = meta.get('tile_crc')
+    if tc is None:
+        return None
+    try:
+        off, T = tc['offset'], tc['tiles']
+        ok = isinstance(off, int) and isinstance(T, int) and not isinstance(off, bool) and not isinstance(T, bool)
+    except (KeyError, TypeError):
+        ok = False
+    if not ok:
+        raise ValueError(f'{path}: corrupt metadata (tile_crc {tc!r})')
+    if meta.get('method') != 'rice':
+        raise ValueError(f"{path}: a per-tile CRC table in a file whose method is {meta.get('method')!r}")
+    if off != int(bundle_bytes) + (-int(bundle_bytes) % 8):
+        raise ValueError(f'{path}: the per-tile CRC table is recorded at {off}, the bundle ends at {bundle_bytes}')
+    try:
+        want = sum(_meta_tile_counts(meta))
+    except (KeyError, TypeError, IndexError) as e:
+        raise ValueError(f'{path}: corrupt metadata ({e!r})') from None
+    if T != want:
+        raise ValueError(f'{path}: the per-tile CRC table records {T} tiles, the shapes in the metadata have {want}')
+    if off + 4 * T > avail:
+        raise ValueError(f'{path}: truncated per-tile CRC table ({off + 4 * T} bytes recorded, {max(avail, 0)} present)')
+    return off, T
 
 
 def _meta_shapes(meta):
@@ -500,11 +643,15 @@ def _pread_exact(fd, view, offset, path):
         raise ValueError(f'{path}: truncated ({view.size} bytes at {offset} not present)')
 
 
-def _region_windows(fd, path, base, nbytes, rplan, plan):
+def _region_windows(fd, path, base, nbytes, rplan, plan, crc_table=None):
     """The table, side-information and payload windows of every range of ``plan`` read from the
     bundle at file offset ``base`` into ONE pinned buffer.  Every value read is validated before it
     sizes a read or a launch.  Returns ``(pinned buffer, bytes used, [(array entry, range, offsets in
-    the buffer: toff, params, bw, payload, payload_first, payload_words)], payload bytes read)``."""
+    the buffer: toff, params, bw, payload, payload_first, payload_words)], payload bytes read, per
+    range the buffer offset of its tiles' CRC entries)``.  ``crc_table = (offset of the file's
+    per-tile CRC table from the bundle's start, T)`` (validated by the caller) reads the touched
+    tiles' u32 entries into the same buffer -- each range's are contiguous -- or the whole table at
+    once when that is fewer reads and it is small; without it the last result is empty."""
     poff, words = rplan['poff'], rplan['words']
     if rplan['total'] > nbytes:
         raise ValueError(f'{path}: the bundle records {rplan["total"]} bytes, the file holds {nbytes}')
@@ -540,6 +687,21 @@ def _region_windows(fd, path, base, nbytes, rplan, plan):
             jobs.append((ar, rng, tab, (o_t, o_p, o_b, o_w, tl[0], pw), (side + 256 * t0, nside,
                                                                            side + ((nb + 7) & ~7) + 256 * t0)))
             payload_bytes += 4 * pw
+    crc_reads, crc_offs = [], []  # (buffer offset, bytes, file offset from the bundle's start)
+    if crc_table is not None and jobs:
+        c_off, T = crc_table
+        begins = _tile_begins([_tiles(n) for n in rplan['ns']])
+        spans = [(begins[ar['index']] + rng[0] // _TILE, (rng[1] - 1) // _TILE - rng[0] // _TILE + 1)
+                 for ar, rng, *_ in jobs]  # (first global tile, tiles) per range
+        if len(jobs) > 1 and 4 * T <= _CRC_TABLE_WHOLE:
+            crc_reads.append((used, 4 * T, c_off))
+            crc_offs = [used + 4 * g for g, _ in spans]
+            used = (used + 4 * T + 7) & ~7
+        else:
+            for g, cnt in spans:
+                crc_reads.append((used, 4 * cnt, c_off + 4 * g))
+                crc_offs.append(used)
+                used = (used + 4 * cnt + 7) & ~7
     buf = dev.pinned_staging(max(used, 8), 'region')
     hv = buf.numpy()
     out = []
@@ -551,10 +713,12 @@ def _region_windows(fd, path, base, nbytes, rplan, plan):
         if pw:
             _pread_exact(fd, hv[o_w:o_w + 4 * pw], base + poff + 4 * w0, path)
         out.append((ar, rng, offs))
-    return buf, used, out, payload_bytes
+    for o, nb_, f_o in crc_reads:
+        _pread_exact(fd, hv[o:o + nb_], base + f_o, path)
+    return buf, used, out, payload_bytes, crc_offs
 
 
-def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, verify=False):
+def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, verify=False, tile_crc=True):
     """``decompress(path)[b0:b1, z0:z1]`` -- bit for bit, shape ``[b1 - b0, z1 - z0, H, W, C...]`` in
     the file's sample dtype -- reading, uploading and decoding only what the selection needs.
     ``batch=(b0, b1)`` selects items of the leading axis (any file: "tile 37" of a tiled file is
@@ -564,9 +728,14 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
 
     Integrity: a partial read cannot check the bundle's CRC-32 and does not.  Every table entry read
     is validated on the host, and the decode checks the side information of every tile it touches
-    (a corrupt touched tile raises ValueError); corruption in tiles the selection does not touch is
-    not noticed.  ``verify=True`` first reads and CRC-checks the whole bundle, then decodes only the
-    region.
+    (a corrupt touched tile raises ValueError).  A file written with ``tile_crc=True`` carries one
+    CRC-32 per tile: the entries of the touched tiles are read with the windows, uploaded in the same
+    transfer and compared on the device (``kmp_rice_tile_crc`` over the very windows the decode
+    reads), their counter returned by the read's one synchronisation -- a damaged touched tile raises
+    ValueError (``tile_crc=False`` skips the check; ``last_timing['tile_crc']`` says whether it ran).
+    Without a table, damage that keeps a touched tile's side information consistent decodes to wrong
+    samples silently.  Corruption in tiles the selection does not touch is not noticed either way.
+    ``verify=True`` first reads and CRC-checks the whole bundle, then decodes only the region.
 
     Files without a v2 Rice bundle ('planes' files, version-1 files) are read by a full
     :func:`decompress` plus a slice (``last_timing['partial']`` is False).  Host and device memory
@@ -592,12 +761,15 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
             z0, z1 = _clamp_range(planes, out.shape[1], 'planes')
             out = out[b0:b1, z0:z1] if planes is not None else out[b0:b1]
             last_timing.update(partial=False, tiles_decoded=0, tiles_total=0, payload_bytes_read=int(nbytes),
-                               bundle_bytes=int(nbytes), total=time.perf_counter() - t0)
+                               bundle_bytes=int(nbytes), total=time.perf_counter() - t0, tile_crc=False)
             return np.ascontiguousarray(out) if as_numpy else out.contiguous()
         try:
             plan = plan_region(meta, planes, batch)
         except (KeyError, TypeError, IndexError) as e:
             raise ValueError(f'{path}: corrupt metadata ({e!r})') from None
+        # the file's per-tile CRC table, checked against the file's size and the metadata's shapes
+        # before anything is sized from it
+        trailer = _tile_crc_trailer(meta, nbytes, os.fstat(fd).st_size - base, path) if tile_crc else None
         count = packing._RHEAD.unpack(hb)[2]
         if not 1 <= count <= packing._MAX_ARRAYS:
             raise ValueError(f'{path}: bad rice bundle header (count {count})')
@@ -613,7 +785,7 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
             raise ValueError(f'{path}: the bundle\'s arrays do not match the metadata\'s levels')
         dtype = dev.CODE_TO_TORCH[rplan['codes'][0]]
         pred = _decode_predictor(path, meta, predictor, dtype)
-        buf, used, jobs, payload_bytes = _region_windows(fd, path, base, nbytes, rplan, plan)
+        buf, used, jobs, payload_bytes, crc_offs = _region_windows(fd, path, base, nbytes, rplan, plan, trailer)
     t1 = time.perf_counter()
     # ---- one upload of all windows, one ranged decode per run of 32 same-dtype records into the
     # local arrays (planes outside the selection stay unwritten: the z-region never reads them) ----
@@ -627,8 +799,13 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
         t = local[i]
         records.append((rplan['codes'][i], t.data_ptr() + dst * t.element_size(), rplan['ns'][i], first, end,
                         wp + o_p, wp + o_b, wp + o_t, wp + o_w, w0, pw))
-    bad = torch.zeros((1,), dtype=torch.int64, device='cuda')
+    bad = torch.zeros((2,), dtype=torch.int64, device='cuda')  # [inconsistent tiles, tile CRC mismatches]
     tiles = packing._launch_ranges(records, bad) if records else 0
+    if crc_offs:  # the touched tiles' CRCs over the same windows, compared with the file's entries on the device
+        packing._launch_tile_crc(
+            [(rplan['ns'][ar['index']], first // _TILE, (end - 1) // _TILE, wp + o_p, wp + o_b, wp + o_t,
+              wp + o_t + 8 * ((end - 1) // _TILE - first // _TILE + 1), wp + o_w, w0, pw, None, wp + o_e)
+             for (ar, (first, end, _), (o_t, o_p, o_b, o_w, w0, pw)), o_e in zip(jobs, crc_offs)], bad[1:])
     # ---- the pyramid, coarsest level first, each level's z-region on its local arrays ----
     ndim, padding = meta['ndim'], meta['padding']
     nmaps = _nd.NMAPS[ndim]
@@ -659,14 +836,16 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
             x = x.contiguous()
     if meta.get('sample_dtype') == 'float32':
         x = x.contiguous().view(torch.float32)
-    nbad = int(bad.item())  # the synchronisation
+    nbad, ncrc = bad.tolist()  # the synchronisation
     if nbad:
         raise ValueError(f'{path}: side information is inconsistent in {nbad} of the {tiles} tiles read (corrupt file)')
+    if ncrc:
+        raise ValueError(f'{path}: tile CRC mismatch in {ncrc} of the {tiles} tiles read (corrupt file)')
     t2 = time.perf_counter()
     out = dev.to_host(x) if as_numpy else x.contiguous()
     t3 = time.perf_counter()
     last_timing.clear()
     last_timing.update(read=t1 - t0, device=t2 - t1, d2h=t3 - t2, total=t3 - t0, partial=True,
                        tiles_decoded=int(tiles), tiles_total=int(plan['tiles_total']),
-                       payload_bytes_read=int(payload_bytes), bundle_bytes=int(nbytes))
+                       payload_bytes_read=int(payload_bytes), bundle_bytes=int(nbytes), tile_crc=bool(crc_offs))
     return out

@@ -482,14 +482,8 @@ def _launch_ranges(records, bad):
     return tiles
 
 
-def unpack_ranges(blob, requests):
-    """Sample ranges of the arrays of a resident v2 Rice bundle: ``requests`` is a list of
-    ``(array_index, first, end)`` flat sample ranges (``0 <= first < end <= n``); returns a list of
-    1-D arrays, ``result[i] == unpack_encoded(blob) array[array_index].reshape(-1)[first:end]`` bit
-    for bit (numpy in -> numpy out).  Only the 16384-sample tiles a range touches are decoded (one
-    launch per run of at most 32 same-dtype requests, one synchronisation for the per-tile
-    consistency counter: a corrupt touched tile raises ValueError, an untouched one is not looked
-    at).  'planes' blobs have no tile table and raise ValueError."""
+def _resident_bundle(blob):
+    """``(device bytes (8-aligned), kind, checked layout)`` of a resident v2 Rice bundle."""
     b, kind = dev.to_device(blob)
     if b.dtype != torch.uint8 or b.dim() != 1:
         raise ValueError('a blob is a 1-D uint8 array')
@@ -508,6 +502,18 @@ def unpack_ranges(blob, requests):
         plan = _remember(_DEC_PLANS, key, _rice_dec_plan(b, hb))
     if plan['total'] > b.numel():
         raise ValueError(f'truncated bundle ({b.numel()} < {plan["total"]} bytes)')
+    return b, kind, plan
+
+
+def unpack_ranges(blob, requests):
+    """Sample ranges of the arrays of a resident v2 Rice bundle: ``requests`` is a list of
+    ``(array_index, first, end)`` flat sample ranges (``0 <= first < end <= n``); returns a list of
+    1-D arrays, ``result[i] == unpack_encoded(blob) array[array_index].reshape(-1)[first:end]`` bit
+    for bit (numpy in -> numpy out).  Only the 16384-sample tiles a range touches are decoded (one
+    launch per run of at most 32 same-dtype requests, one synchronisation for the per-tile
+    consistency counter: a corrupt touched tile raises ValueError, an untouched one is not looked
+    at).  'planes' blobs have no tile table and raise ValueError."""
+    b, kind, plan = _resident_bundle(blob)
     reqs = []
     for req in requests:
         ai, first, end = (int(v) for v in req)
@@ -551,6 +557,77 @@ def unpack_ranges(blob, requests):
     if nbad:
         raise ValueError(f'rice bundle side information is inconsistent in {nbad} of the tiles read (corrupt bundle)')
     return [dev.from_device(o, kind) for o in outs]
+
+
+# ---------------------------------------------------------------------------------------------
+# per-tile CRCs of a rice bundle (kmp_rice_tile_crc): zlib.crc32 of each tile's params, bw and
+# payload words, in the bundle's global tile order; the pieces of a record are separate pointers,
+# into a resident bundle (tile_crcs, container._bundle) or at windows read from a file
+# (container.read_region)
+# ---------------------------------------------------------------------------------------------
+
+def tile_begins(ns):
+    """The global index of every array's first tile: the prefix sum of the arrays' tile counts."""
+    out, t = [], 0
+    for n in ns:
+        out.append(t)
+        t += _tiles_of(n)
+    return out, t
+
+
+def _tiles_of(n):
+    return -(-(-(-n // 64)) // _TILE_BLOCKS) if n > 0 else 0
+
+
+def _launch_tile_crc(records, bad):
+    """``kmp_rice_tile_crc`` over ``records`` -- tuples ``(n, t0, t1, params ptr, bw ptr, toff ptr,
+    closing ptr, payload ptr, payload_first, payload_words, crc_out ptr or None, expect ptr or
+    None)`` -- at most 32 per launch; no synchronisation.  Returns the tiles covered."""
+    tiles = 0
+    for i in range(0, len(records), 32):
+        chunk = records[i:i + 32]
+        arr = (_lib.RiceCrcRange * len(chunk))()
+        for q, r in enumerate(chunk):
+            (arr[q].n, arr[q].t0, arr[q].t1, arr[q].params, arr[q].bw, arr[q].toff, arr[q].closing, arr[q].payload,
+             arr[q].payload_first, arr[q].payload_words, arr[q].crc_out, arr[q].expect) = r
+            tiles += r[2] - r[1] + 1
+        check(lib.kmp_rice_tile_crc(arr, len(chunk), bad.data_ptr() if bad is not None else None, dev.stream()),
+              'rice tile crc')
+    return tiles
+
+
+def _resident_crc_records(base, ns, offs, poff, payload_words, table_ptr, expect=False):
+    """One record per non-empty array of the bundle resident at device address ``base``: all of the
+    array's tiles, the closing word of its last tile read from its record's end-word field, the
+    CRCs written to (or, ``expect``, compared with) the u32 table at ``table_ptr`` in global tile
+    order."""
+    begins, _ = tile_begins(ns)
+    records = []
+    for i, (n, (side, toff), t0) in enumerate(zip(ns, offs, begins)):
+        nt = _tiles_of(n)
+        if not nt:
+            continue
+        tab = table_ptr + 4 * t0
+        records.append((n, 0, nt - 1, base + side, base + side + _pad8(-(-n // 64)), base + toff,
+                        base + _RHEAD.size + _RREC.size * i + 120, base + poff, 0, payload_words,
+                        None if expect else tab, tab if expect else None))
+    return records
+
+
+def tile_crcs(blob):
+    """The per-tile CRC-32 table of a resident v2 Rice bundle: uint32 ``[T]`` in the bundle's global
+    tile order (arrays in bundle order, each array's tiles in order), entry ``tile_begin[a] + t`` =
+    ``zlib.crc32(params[256 t : 256 t + nbk] + bw[256 t : 256 t + nbk] + the tile's payload words
+    as little-endian bytes)``.  One launch per 32 arrays; numpy in -> numpy out.  'planes' blobs have
+    no tiles and raise ValueError."""
+    b, kind, plan = _resident_bundle(blob)
+    out = torch.zeros((max(plan['T'], 1),), dtype=torch.int32, device='cuda')[:plan['T']]
+    if plan['T']:
+        records = _resident_crc_records(b.data_ptr(), plan['ns'], plan['offs'], plan['poff'], plan['words'],
+                                        out.data_ptr())
+        _launch_tile_crc(records, None)
+    out = out.view(torch.uint32)
+    return dev.from_device(out, kind)
 
 
 # ---------------------------------------------------------------------------------------------
