@@ -13,7 +13,8 @@ restricted axis is odd (``dims`` = 0: the parity maps are one entry shorter), th
 LinearPredictor rows of the generic row kernel (``fuse_lin2d``), and a volume region that also
 restricts y and x.  Reference: the oracle (mean / f32 rows); for bf16x2 rows, which the oracle does
 not equal bit for bit by design, the same request through the two-pass path
-(KMP_DISABLE_LINEAR_FUSED=1) in plain tensors.  A reference is computed once per (row, pattern) at
+(KMP_DISABLE_LINEAR_FUSED=1) in plain tensors, whose out-of-range cells test_gpu_linear_casts.py pins
+to the specification.  A reference is computed once per (row, pattern) at
 the largest batch the row runs; smaller batches are its leading items (every step of the codec is
 per batch item)."""
 
@@ -123,14 +124,29 @@ def _clamp_weights(p, ndim, dtype):
     return w, b
 
 
+def _assert_both_clamps(ons, x, w, b, p, dtype, split):
+    """From the float64 value alone (of the bf16x2 split weights for ``split``), with the 1e-5 margin
+    that bounds either arithmetic's distance from it: some predictions lie at or below -1, some at or
+    above max + 1, some inside the range, whichever arithmetic evaluates them."""
+    lowres = ons.pad_neighborhood(ons.lowres_from_highres(ons.pad_highres(x)[0]), p)
+    feats = ons.features_from_lowres(lowres, p)
+    v = OP.linear_bf16x2_split(feats, w, b) if split else OP.linear_predictions(feats, w, b, dtype)[0]
+    nd = feats.ndim - 2
+    scale = np.tensordot(np.moveaxis(np.abs(feats.astype(np.float64)), nd, -1), np.abs(w.astype(np.float64)),
+                         axes=([-1], [0]))
+    m = 1e-5 * (np.moveaxis(scale, -1, nd) + np.abs(b.astype(np.float64)).reshape(-1, 1))
+    top = np.iinfo(dtype).max
+    assert (v <= -1.0 - m).any() and (v >= top + 1.0 + m).any() and ((v > m) & (v < top - m)).any()
+
+
 def _predictor_for(kom, row, pattern):
     _, shape, dtype, kind, p, *_ = row
     ndim = len(shape) - 2
     key = (kind, p, ndim, np.dtype(dtype).name, pattern == 'clamp')
     if key not in _PRED:
         if pattern == 'clamp':
-            assert kind == 'f32'
-            _PRED[key] = kom.LinearPredictor(*_clamp_weights(p, ndim, dtype), p, ndim, arith='f32')
+            assert kind in ('f32', 'bf16x2')
+            _PRED[key] = kom.LinearPredictor(*_clamp_weights(p, ndim, dtype), p, ndim, arith=kind)
         else:
             _PRED[key] = _predictor(kom, kind, p, ndim, dtype)
     return _PRED[key]
@@ -146,6 +162,8 @@ def _reference(kom, kmp_opt, row, pattern):
     ns, ons = _ns(kom, ndim)
     x = _pattern((_bmax(row),) + tuple(shape[1:]), dtype, pattern)
     pred = _predictor_for(kom, row, pattern)
+    if kind in ('f32', 'bf16x2') and pattern == 'clamp':
+        _assert_both_clamps(ons, x[:shape[0]], pred.weights.numpy(), pred.bias.numpy(), p, dtype, kind == 'bf16x2')
     if kind == 'bf16x2':  # the two-pass path on the same arithmetic, in plain tensors
         kmp_opt('KMP_DISABLE_LINEAR_FUSED', 1)
         last = lambda: kom._lib.lib.kmp_last_launch().decode()  # noqa: E731
@@ -322,9 +340,10 @@ def test_guard_batches(kom, kmp_opt, rid):
 
 @pytest.mark.parametrize('rid', IDS)
 def test_guard_patterns(kom, kmp_opt, rid):
-    """All-max, the 0 / max checkerboard and (f32 linear) predictions that leave [0, max]."""
+    """All-max, the 0 / max checkerboard and (LinearPredictor rows, either arithmetic) predictions
+    that leave [0, max]."""
     row = ROW_BY_ID[rid]
-    for pattern in ('max', 'checker') + (('clamp',) if row[3] == 'f32' else ()):
+    for pattern in ('max', 'checker') + (('clamp',) if row[3] in ('f32', 'bf16x2') else ()):
         run_case(kom, kmp_opt, row, Case(_own(row), None, pattern))
         run_case(kom, kmp_opt, row, Case(_own(row), 'end', pattern))
 
