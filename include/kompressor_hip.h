@@ -330,6 +330,11 @@ int64_t kmp_rice_bundle_workspace_bytes(int64_t tiles_total);
 /* byte payload_off); the tile of global index tiles_total - 1 writes the bundle's payload words */
 /* (u64 at byte 56) and byte size (u64 at byte 64).  Calls for one bundle go in tile order on    */
 /* one stream (replaces round 2's kmp_rice_plan / kmp_rice_pack and their two scan launches).   */
+/* Capacity: ``bundle`` (8-byte aligned) holds at least payload_off + worst bytes, worst = the sum */
+/* over all arrays of the bundle of ceil(n / 64) * (2 W + 2) * 4 (a block codes into at most       */
+/* 2 W + 2 words, W the sample bits).  The caller writes the header [0, 80 + 128 * arrays); the    */
+/* launches write the rest up to the byte size ``total`` they store at byte 64, total <=           */
+/* payload_off + worst, and no byte at or past ``total`` (tests/test_gpu_guard_packing.py).        */
 int kmp_rice_bundle_encode(int32_t dtype, const kmp_rice_array* arrays, int32_t count, int64_t tile_begin,
                            int64_t tiles_total, uint8_t* bundle, int64_t payload_off, void* workspace,
                            kmp_stream_t stream);

@@ -113,6 +113,11 @@ def _box_mask(shape, box, nsp):
     return m
 
 
+def copy_box_mask(shape, offsets, extents, nsp):
+    """True over ``[:, o:o + e per spatial axis, ...]``: what a box copy into an array of ``shape`` owns."""
+    return _box_mask(shape, [(int(o), int(o) + int(e)) for o, e in zip(offsets, extents)], nsp)
+
+
 def encode_masks(lowres_shape, map_shapes, region, nsp):
     """``{'lowres': mask, 'map0': mask, ...}`` for an encode launch with ``region``.  ``map_shapes``
     are the trimmed map shapes (the oracle's outputs): a map entry is owned iff its coordinate is in
@@ -157,7 +162,7 @@ def _split(c):
     return a[:lo], a[lo:lo + c.nbytes], a[lo + c.nbytes:]
 
 
-def check_launch_pair(run, inputs, outputs, expected, masks, untouched=()):
+def check_launch_pair(run, inputs, outputs, expected, masks, untouched=(), predicates=None):
     """``run(sentinel)`` performs one launch on arenas filled with ``sentinel`` and returns
     ``{name: Carved}`` of EVERY tensor the launch was given (inputs, outputs, workspace).
     ``inputs``: ``{name: numpy array}`` the input payloads were filled with; ``outputs``: names of
@@ -165,6 +170,10 @@ def check_launch_pair(run, inputs, outputs, expected, masks, untouched=()):
     ``{name: bool array}``, the elements the launch owns.  Tensors named in neither ``inputs`` nor
     ``outputs`` (the workspace) are scratch: only their guards are checked, unless they are named
     in ``untouched`` (a launch that must write nothing at all: the payload still the sentinel).
+    ``predicates``: ``{name: (numpy dtype, wrong)}`` for an output whose owned values are not pinned
+    bit for bit: ``wrong(values)`` gets the payload as an array of that dtype and the tensor's shape
+    and returns the bool array of elements that miss the output's bound; it replaces the bytewise
+    comparison of check c for that output (``expected`` needs no entry for it), nothing else.
 
     Raises :class:`GuardError` listing every violation of
       a. guard, shift and input bytes unchanged;
@@ -218,11 +227,18 @@ def check_launch_pair(run, inputs, outputs, expected, masks, untouched=()):
             if stray.any():
                 n, txt = _elem_report(stray, shape, item)
                 fail('unowned', name, n, f'elements written outside the launch\'s box {tag}: {txt}')
-            # c. everything inside equals the reference
-            want = np.ascontiguousarray(expected[name])
-            assert tuple(want.shape) == shape and want.dtype.itemsize == item, \
-                f'{name}: expected {want.shape} {want.dtype}, tensor is {shape} x {item} B'
-            wrong = mflat & (elems != want.reshape(-1).view(np.uint8).reshape(-1, item)).any(axis=1)
+            # c. everything inside equals the reference (or meets the caller's bound)
+            if predicates and name in predicates:
+                pdtype, judge = predicates[name]
+                assert np.dtype(pdtype).itemsize == item, f'{name}: predicate dtype {pdtype} is not {item} B'
+                miss = np.asarray(judge(body.copy().view(pdtype).reshape(shape)), dtype=bool)
+                assert miss.shape == shape, f'{name}: predicate returned shape {miss.shape}, tensor is {shape}'
+                wrong = mflat & miss.reshape(-1)
+            else:
+                want = np.ascontiguousarray(expected[name])
+                assert tuple(want.shape) == shape and want.dtype.itemsize == item, \
+                    f'{name}: expected {want.shape} {want.dtype}, tensor is {shape} x {item} B'
+                wrong = mflat & (elems != want.reshape(-1).view(np.uint8).reshape(-1, item)).any(axis=1)
             if wrong.any():
                 n, txt = _elem_report(wrong, shape, item)
                 fail('value', name, n, f'owned elements differ from the reference {tag}: {txt}')

@@ -314,3 +314,87 @@ def test_masks_restrict_every_axis():
     want[:, 1:3, 2:4, 0:2] = True
     assert np.array_equal(e['map0'], want) and e['lowres'].sum() == 3 * 3 * 2
     assert not G.encode_masks(lo_shape, [], [(2, 2), (0, 5), (0, 6)], 3)['lowres'].any()
+
+
+# ---------------------------------------------------------------------------------------------
+# box copies and outputs judged by a predicate (the helpers of the C-ABI guard modules)
+# ---------------------------------------------------------------------------------------------
+
+def test_copy_box_mask_is_the_box():
+    m = G.copy_box_mask((2, 5, 6, 7, 3), (1, 0, 4), (3, 2, 3), 3)
+    want = np.zeros((2, 5, 6, 7, 3), bool)
+    want[:, 1:4, 0:2, 4:7, :] = True
+    assert np.array_equal(m, want)
+    m2 = G.copy_box_mask((3, 4, 9, 1), (2, 1), (2, 0), 2)
+    assert m2.shape == (3, 4, 9, 1) and not m2.any()  # an empty extent owns nothing
+
+
+def _box_launch(extra=None):
+    """A 'box copy' of a float32 source into dst[:, 1:3, 2:5], written by numpy into CPU arenas."""
+    src = np.arange(2 * 2 * 3, dtype=np.float32).reshape(2, 2, 3, 1) + 0.5
+    shape = (2, 4, 6, 1)
+    mask = G.copy_box_mask(shape, (1, 2), (2, 3), 2)
+    want = np.zeros(shape, np.float32)
+    want[:, 1:3, 2:5] = src
+
+    def run(sentinel):
+        t = {'src': G.fill(G.carve_arena(src.shape, torch.float32, 'cpu', sentinel), src),
+             'dst': G.carve_arena(shape, torch.float32, 'cpu', sentinel)}
+        t['dst'].payload.numpy()[:, 1:3, 2:5] = src
+        if extra is not None:
+            extra(t, sentinel)
+        return t
+
+    return run, {'src': src}, ['dst'], {'dst': want}, {'dst': mask}, want
+
+
+def test_box_copy_passes_and_a_store_past_the_box_is_unowned():
+    run, inputs, outputs, expected, masks, _ = _box_launch()
+    G.check_launch_pair(run, inputs, outputs, expected, masks)
+
+    def spill(t, sentinel):  # one element past the box's x end, inside dst
+        t['dst'].payload.numpy()[1, 2, 5, 0] = 7.0
+
+    run, inputs, outputs, expected, masks, _ = _box_launch(spill)
+    with pytest.raises(G.GuardError) as e:
+        G.check_launch_pair(run, inputs, outputs, expected, masks)
+    assert [(c, n) for c, n, _ in e.value.failures] == [('unowned', 'dst')] * 2
+
+
+def test_predicate_replaces_only_the_value_comparison():
+    run, inputs, outputs, _, masks, want = _box_launch()
+    near = lambda v: np.abs(v.astype(np.float64) - want) > 0.25  # noqa: E731
+    seen = []
+
+    def judge(v):
+        seen.append((v.dtype, v.shape))
+        return near(v)
+
+    G.check_launch_pair(run, inputs, outputs, {}, masks, predicates={'dst': (np.float32, judge)})
+    assert seen == [(np.dtype(np.float32), (2, 4, 6, 1))] * 2
+
+    def off_by_a_little(t, sentinel):  # within the bound: passes; bytewise it would not
+        t['dst'].payload.numpy()[0, 1, 2, 0] += 0.125
+
+    run, inputs, outputs, expected, masks, _ = _box_launch(off_by_a_little)
+    G.check_launch_pair(run, inputs, outputs, {}, masks, predicates={'dst': (np.float32, near)})
+    with pytest.raises(G.GuardError) as e:
+        G.check_launch_pair(run, inputs, outputs, expected, masks)
+    assert {(c, n) for c, n, _ in e.value.failures} == {('value', 'dst')}
+
+    def off_by_a_lot(t, sentinel):
+        t['dst'].payload.numpy()[0, 1, 2, 0] += 1.0
+
+    run, inputs, outputs, _, masks, _ = _box_launch(off_by_a_lot)
+    with pytest.raises(G.GuardError) as e:
+        G.check_launch_pair(run, inputs, outputs, {}, masks, predicates={'dst': (np.float32, near)})
+    assert [(c, n, k) for c, n, k in e.value.failures] == [('value', 'dst', 1)] * 2
+
+    def spill_and_depend(t, sentinel):  # the other checks still apply to a predicate output
+        t['dst'].payload.numpy()[1, 0, 0, 0] = 3.0
+        t['dst'].payload.numpy()[0, 1, 2, 0] += 0.001 * sentinel
+
+    run, inputs, outputs, _, masks, _ = _box_launch(spill_and_depend)
+    with pytest.raises(G.GuardError) as e:
+        G.check_launch_pair(run, inputs, outputs, {}, masks, predicates={'dst': (np.float32, near)})
+    assert {(c, n) for c, n, _ in e.value.failures} == {('unowned', 'dst'), ('nondeterministic', 'dst')}
