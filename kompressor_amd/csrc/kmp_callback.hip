@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "kmp_codec.h"
+#include "kmp_primitives.h"
 
 namespace kmp {
 namespace cb {
@@ -505,8 +506,7 @@ static int window_launch(int nsp, int dtype, const void* src, int mult, const in
   if (total == 0) return KMP_OK;
   return dispatch_any_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
-    const int64_t src_n = B * S[0] * S[1] * S[2] * C;
-    if (C == 1 && total < ((int64_t)1 << 30) && src_n < ((int64_t)1 << 30) && !opt(OPT_DISABLE_ROWS, 0)) {
+    if (rows_ok(C, {total, B * S[0] * S[1] * S[2] * C})) {
       const int64_t nch = ceil_div(W[2], Vec16<T>::V), items = B * W[0] * W[1] * nch;
       rows_window_kernel<T><<<grid_for(items), kThreads, 0, stream>>>(
           (const T*)src, (int32_t)S[0], (int32_t)S[1], (int32_t)S[2], g, mult, nsp == 3 ? p : 0, p, (int32_t)W[0],
@@ -568,11 +568,7 @@ int kmp_encode_with_predictions_typed(int32_t nsp, int32_t dtype, int32_t coder,
   const Geo g = make_geo_from_highres(nsp, shape);
   CMapPtrs pp{};
   MapPtrs mp{};
-  for (int k = 0; k < (nsp == 3 ? 7 : 3); ++k) {
-    KMP_REQUIRE(preds[k] && maps_out[k], "null map pointer");
-    pp.p[k] = preds[k];
-    mp.p[k] = maps_out[k];
-  }
+  KMP_REQUIRE(bind_maps(nsp, preds, pp) && bind_maps(nsp, maps_out, mp), "null map pointer");
   const int64_t total = B * g.E[0] * g.E[1] * g.E[2] * C;
   if (total == 0) return KMP_OK;
   const bool small = C == 1 && B * g.n[0] * g.n[1] * g.n[2] < ((int64_t)1 << 31) &&
@@ -624,11 +620,7 @@ int kmp_decode_with_predictions_typed(int32_t nsp, int32_t dtype, int32_t coder,
   }
   const Geo g = make_geo_from_lowres(nsp, shape, dims);
   CMapPtrs pp{}, mp{};
-  for (int k = 0; k < (nsp == 3 ? 7 : 3); ++k) {
-    KMP_REQUIRE(preds[k] && maps[k], "null map pointer");
-    pp.p[k] = preds[k];
-    mp.p[k] = maps[k];
-  }
+  KMP_REQUIRE(bind_maps(nsp, preds, pp) && bind_maps(nsp, maps, mp), "null map pointer");
   const int64_t total = B * g.E[0] * g.E[1] * g.E[2] * C;
   if (total == 0) return KMP_OK;
   const bool small = C == 1 && B * g.n[0] * g.n[1] * g.n[2] < ((int64_t)1 << 31) &&

@@ -173,6 +173,33 @@ def test_mean_predict_maps(kom, form, dtype, case):
                 assert name.startswith(family), (name, family)
 
 
+# (dtype, channel counts) no LDS kernel serves: the cell means, then the per-element aggregation of them
+MEAN_ELEMENT = [(np.int32, (1, 2)), (np.uint32, (1, 2)), (np.uint8, (2,)), (np.uint16, (2,))]
+
+
+@pytest.mark.parametrize('nsp', [3, 2])
+@pytest.mark.parametrize('dtype,channels', MEAN_ELEMENT, ids=[np.dtype(d).name for d, _ in MEAN_ELEMENT])
+def test_mean_predict_maps_elements(kom, form, dtype, channels, nsp):
+    """The two-pass element fallback (cell_mean_map_kernel, then the cell-means form of the element
+    aggregation in its general <T, I> instantiation) on full-range samples: 32-bit samples at C == 1 and
+    C == 2, u8 / u16 at C == 2, maps of the sample dtype through both entry points."""
+    code = CODE[np.dtype(dtype)]
+    for C in channels:
+        shape = (2, 5, 6, 7, C) if nsp == 3 else (3, 7, 9, C)
+        for p in (0, 1, 2):
+            window = ons(nsp).pad_neighborhood(K.rand(shape, dtype, shape[-2] + 3 * p + C), p)
+            S = window.shape[1:1 + nsp]
+            maps = [np.ascontiguousarray(m) for m in OP.mean_predictions_fn(p, nsp)(window)]
+            assert len(maps) == NMAPS[nsp] and all(m.dtype == np.dtype(dtype) for m in maps)
+            for entry, typed in (('kmp_mean_predict_maps', ()), ('kmp_mean_predict_maps_typed', (code,))):
+                for shift in K.SHIFTS:
+                    outs = _named('map', maps, 'out')
+                    name = K.launch(entry, [T('window', 'in', window)] + outs,
+                                    lambda fn, q: fn(nsp, code, *typed, q['window'], shape[0], K.i64x3(S), C, p,
+                                                     _ptrs(q, outs), None), shift)
+                    assert name == 'mean_predict_maps'
+
+
 # ---------------------------------------------------------------------------------------------
 # maps_from_predictions
 # ---------------------------------------------------------------------------------------------

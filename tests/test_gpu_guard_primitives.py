@@ -1,5 +1,6 @@
 """Guard bands, exact ownership and off-alignment pointers for the geometry primitives and the
-coders of the C-ABI (kmp_primitives.hip, kmp_tiles.hip, kmp_categorical.hip), called directly through
+coders of the C-ABI (kmp_primitives.hip, kmp_tiles.hip, kmp_categorical.hip; the predictor primitives
+of kmp_maps_from_predictions.hip and kmp_mean_predict.hip: test_gpu_guard_callback.py), called directly through
 ``kompressor_amd._lib.lib`` with pointers into sentinel-filled arenas (guard_capi.py, guard_spec.py).
 
 Per launch, twice (0xA5 / 0x5A arenas): guards, shift bytes and inputs unchanged; output elements the

@@ -122,7 +122,7 @@ def test_coders_keep_torch(kom):
 
 def _mp_lds_bytes(window_shape, itemsize, padding, q):
     """The LDS of the per-plane mean predictor kernel with q output planes per workgroup
-    (kmp_primitives.hip, kmp_mean_predict_maps): which variant a window gets."""
+    (kmp_mean_predict.hip, kmp_mean_predict_maps): which variant a window gets."""
     S1, S2 = window_shape[2], window_shape[3]
     c1, c2 = S1 - 2 * padding - 1, S2 - 2 * padding - 1
     nb = 16 * (-(-(2 * padding + 2 + q) * S1 * S2 * itemsize // 16) + 1)

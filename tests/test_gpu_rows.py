@@ -1,6 +1,7 @@
 """Row kernels of the geometry primitives (kmp_primitives.hip ``rows_*``: C == 1, 16-byte chunks
-of a row, unaligned vectors on interior chunks, per-element edges) vs the oracle / numpy, at row
-lengths around every chunk boundary for each sample size."""
+of a row, unaligned vectors on interior chunks, per-element edges) and the z-rolling LDS kernels of
+kmp_maps_from_predictions.hip and kmp_mean_predict.hip vs the oracle / numpy, at row lengths around
+every chunk boundary for each sample size."""
 
 import numpy as np
 import pytest

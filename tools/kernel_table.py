@@ -2,7 +2,7 @@
 """Per-kernel resource table of every HIP source of a tree, and the comparison of two such tables.
 
     python tools/kernel_table.py table [ROOT [ASMDIR]] > table.txt   # compile ROOT's csrc/*.hip device-only
-    python tools/kernel_table.py diff parent.txt new.txt [--pair OLD_ENC OLD_DEC NEW]
+    python tools/kernel_table.py diff parent.txt new.txt [--pair OLD=NEW:ARG ...]
     python tools/kernel_table.py summary table.txt > summary.txt     # one line per kernel template
 
 A table line is, per kernel symbol, sorted by demangled name:
@@ -13,9 +13,11 @@ Sources are compiled with ``_build.py``'s FLAGS and FILE_FLAGS.  ``body-hash`` i
 instruction text between the kernel's entry label and its ``.Lfunc_end``, basic-block labels
 renumbered in order of appearance, so two tables agree on a kernel exactly when its code does.
 
-``diff --pair encode_generic_kernel decode_generic_kernel codec_generic_kernel`` pairs the old
-kernels ``OLD_ENC<A...>`` / ``OLD_DEC<A...>`` with ``NEW<A..., false>`` / ``NEW<A..., true>``: their
-numbers must agree, their body hashes are reported when they do not.
+``diff --pair OLD=NEW:ARG ...`` pairs every old kernel ``OLD<A...>`` with ``NEW<A..., ARG>``, for any
+number of such mappings: ``encode_generic_kernel=codec_generic_kernel:false
+decode_generic_kernel=codec_generic_kernel:true`` for two kernels merged on a trailing ``bool``.  A
+pair must keep vgpr, agpr, scratch, lds and occupancy; sgpr and code length may move with the kernel
+argument layout and are reported when they do, as is a body hash that differs.
 
 A full table has a line per instantiation (some 1500 of them); ``summary`` condenses one to a line
 per kernel template: the number of instantiations, the range of each number over them, and a digest
@@ -94,30 +96,36 @@ def read_table(path):
     return out
 
 
-def diff(a_path, b_path, pair):
+PAIR_KEEPS = [i for i, (k, _) in enumerate(INFO) if k in ('vgpr', 'agpr', 'scratch', 'lds', 'occ')]
+
+
+def diff(a_path, b_path, pairs):
     a, b = read_table(a_path), read_table(b_path)
     bad = 0
-    if pair:
-        old_enc, old_dec, new = pair
+    mapping = {old: new.rsplit(':', 1) for old, new in (p.split('=', 1) for p in pairs)}
+    if mapping:
         renamed = {}
         for name, row in a.items():
-            m = re.match(r'(void kmp::)(%s|%s)<(.*)>\(' % (old_enc, old_dec), name)
+            m = re.match(r'(void kmp::)(%s)<(.*)>\(' % '|'.join(map(re.escape, mapping)), name)
             if not m:
                 renamed[name] = row
                 continue
-            dec = 'true' if m.group(2) == old_dec else 'false'
-            want = f'{m.group(1)}{new}<{m.group(3)}, {dec}>('
+            new, arg = mapping[m.group(2)]
+            want = f'{m.group(1)}{new}<{m.group(3)}, {arg}>('
             got = [n for n in b if n.startswith(want)]
             if len(got) != 1:
                 print(f'UNPAIRED {name}')
                 bad += 1
                 continue
             nb = b.pop(got[0])
-            if nb[:-1] != row[:-1]:
+            if [nb[i] for i in PAIR_KEEPS] != [row[i] for i in PAIR_KEEPS]:
                 print(f'NUMBERS DIFFER {name}\n  parent {row}\n  new    {nb}')
                 bad += 1
-            elif nb[-1] != row[-1]:
-                print(f'paired, numbers equal, text differs: {got[0]}')
+            elif nb != row:
+                moved = ', '.join(f'{k} {row[i]} -> {nb[i]}' for i, (k, _) in enumerate(INFO) if nb[i] != row[i])
+                print(f'paired, {moved or "numbers equal"}, text differs: {name}\n    -> {got[0]}')
+            else:
+                print(f'paired, identical code: {name}\n    -> {got[0]}')
         a = renamed
     for name in sorted(set(a) | set(b)):
         if name not in a or name not in b:
@@ -149,5 +157,4 @@ if __name__ == '__main__':
     elif sys.argv[1] == 'summary':
         summary(sys.argv[2])
     else:
-        pair = sys.argv[sys.argv.index('--pair') + 1:][:3] if '--pair' in sys.argv else None
-        sys.exit(diff(sys.argv[2], sys.argv[3], pair))
+        sys.exit(diff(sys.argv[2], sys.argv[3], sys.argv[sys.argv.index('--pair') + 1:] if '--pair' in sys.argv else []))
