@@ -36,7 +36,13 @@ typedef enum {
   KMP_ERR_LAUNCH = -3,   /* HIP launch / runtime error */
 } kmp_status;
 
-typedef enum { KMP_U8 = 0, KMP_U16 = 1, KMP_I32 = 2, KMP_F32 = 3, KMP_U32 = 4 } kmp_dtype;
+/* KMP_I8 / KMP_I16: signed samples.  Predictors see M(x) = x ^ signbit (the order-preserving map onto
+ * the unsigned type of the same width) and run the unsigned arithmetic on it; residual maps are the
+ * unsigned type's, (M(gt) - P) mod 2^W; every sample-domain array a caller passes or receives
+ * (highres, lowres, predictions) is in the signed type, bit for bit.  Their natural coders are
+ * KMP_CODER_U8 / KMP_CODER_U16.  The data-movement primitives (lowres, maps, targets, pad, tiles,
+ * copy_box, features) take the same-width unsigned code for them. */
+typedef enum { KMP_U8 = 0, KMP_U16 = 1, KMP_I32 = 2, KMP_F32 = 3, KMP_U32 = 4, KMP_I8 = 5, KMP_I16 = 6 } kmp_dtype;
 
 /* Residual coders, utils.py:28-55 (+ the build's mod-2^32 coder for bit-cast float32). */
 typedef enum { KMP_CODER_RAW = 0, KMP_CODER_U8 = 1, KMP_CODER_U16 = 2, KMP_CODER_U32 = 3 } kmp_coder;
@@ -51,7 +57,8 @@ typedef enum {
   KMP_PRED_LINEAR = 1,
   /* the same predictor on the matrix cores: bf16x2 split of features and weights, one
      v_mfma_f32_16x16x32_bf16 per chunk of 8 features (kmp_bf16x2.h); within the north star's 1e-5
-     of the f64 value rather than bit-equal to the f32 fma chain; uint8 / uint16 samples */
+     of the f64 value rather than bit-equal to the f32 fma chain; uint8 / uint16 samples (a signed
+     dtype with this kind is KMP_ERR_ARG: signed samples take KMP_PRED_LINEAR) */
   KMP_PRED_LINEAR_MFMA = 2,
 } kmp_predictor_kind;
 
@@ -188,7 +195,10 @@ int kmp_mean_predict_maps_typed(int32_t nsp, int32_t dtype, int32_t out_dtype, c
                                 void* const out[7], kmp_stream_t stream);
 
 /* Linear predictor on a padded lowres window: per-cell [B, cells..., K, C] predictions in the
-   dtype (MFMA f32), optionally also the f32 pre-cast values (``preds_f32`` may be NULL). */
+   dtype (MFMA f32), optionally also the f32 pre-cast values (``preds_f32`` may be NULL).
+   KMP_I8 / KMP_I16: the features are M(window), the chain's value is cast in the mapped domain
+   (truncate, saturate to [0, 2^W - 1], NaN -> 0) and stored as M^-1 of it; ``preds_f32`` holds the
+   chain's own (mapped-domain) values. */
 int kmp_linear_predict(int32_t nsp, int32_t dtype, const void* padded_lowres, int64_t B, const int64_t shape[3],
                        int64_t C, int32_t padding, const float* weights, const float* bias, void* preds_out,
                        float* preds_f32, kmp_stream_t stream);
@@ -235,7 +245,9 @@ int kmp_tiles(int32_t nsp, int32_t dtype, int32_t direction, const void* src, co
 
 /* Residual coders utils.py:28-55 on n elements.  ``pred_dtype``/``x_dtype`` are the operand
    dtypes (x = gt for ENCODE, encoded for DECODE); the output is uint8 / uint16 / int32 /
-   uint32 for KMP_CODER_U8 / U16 / RAW / U32. */
+   uint32 for KMP_CODER_U8 / U16 / RAW / U32.  KMP_I8 / KMP_I16 operands with KMP_CODER_U8 / U16:
+   (gt - pred) mod 2^W of the signed values -- the same bits as the unsigned codes give, the sign
+   map cancels in the difference; a decode's output holds the signed sample's bit pattern. */
 int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* pred, int32_t x_dtype,
              const void* x, int64_t n, void* out, kmp_stream_t stream);
 

@@ -15,11 +15,14 @@ import torch
 from . import _lib
 
 TORCH_TO_CODE = {torch.uint8: _lib.U8, torch.uint16: _lib.U16, torch.int32: _lib.I32,
-                 torch.float32: _lib.F32, torch.uint32: _lib.U32}
+                 torch.float32: _lib.F32, torch.uint32: _lib.U32, torch.int8: _lib.I8, torch.int16: _lib.I16}
+# signed samples (int8 / int16): the unsigned dtype of the same width, which carries their residuals
+# and under whose code the data-movement launches take them (they move bits; include/kompressor_hip.h)
+UNSIGNED_TWIN = {torch.int8: torch.uint8, torch.int16: torch.uint16}
 CODE_TO_TORCH = {v: k for k, v in TORCH_TO_CODE.items()}
 NP_TO_TORCH = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16,
                np.dtype(np.int32): torch.int32, np.dtype(np.float32): torch.float32,
-               np.dtype(np.uint32): torch.uint32}
+               np.dtype(np.uint32): torch.uint32, np.dtype(np.int8): torch.int8, np.dtype(np.int16): torch.int16}
 
 _device_checked = False
 
@@ -312,7 +315,18 @@ def dtype_code(t):
         return TORCH_TO_CODE[t.dtype]
     except KeyError:
         raise TypeError(f'kompressor_amd: unsupported dtype {t.dtype} '
-                        f'(supported: uint8, uint16, int32, uint32, float32)') from None
+                        f'(supported: uint8, uint16, int8, int16, int32, uint32, float32)') from None
+
+
+def bits_code(code):
+    """The code a bit-moving launch takes for a stored dtype ``code`` (signed: the unsigned twin's)."""
+    return {_lib.I8: _lib.U8, _lib.I16: _lib.U16}.get(code, code)
+
+
+def move_code(t):
+    """``dtype_code`` for a launch that only moves samples: a signed tensor goes under its
+    same-width unsigned code."""
+    return dtype_code(t) if t.dtype not in UNSIGNED_TWIN else TORCH_TO_CODE[UNSIGNED_TWIN[t.dtype]]
 
 
 _CUDA = torch.device('cuda')

@@ -29,7 +29,7 @@ lib = ctypes.CDLL(LIB_PATH)
 
 # enums (include/kompressor_hip.h)
 KMP_OK, KMP_ERR_ARG, KMP_ERR_UNSUPPORTED, KMP_ERR_LAUNCH = 0, -1, -2, -3
-U8, U16, I32, F32, U32 = 0, 1, 2, 3, 4
+U8, U16, I32, F32, U32, I8, I16 = 0, 1, 2, 3, 4, 5, 6
 CODER_RAW, CODER_U8, CODER_U16, CODER_U32 = 0, 1, 2, 3
 ENCODE, DECODE = 0, 1
 PRED_MEAN, PRED_LINEAR, PRED_LINEAR_MFMA = 0, 1, 2
@@ -216,4 +216,4 @@ def ptrs(tensors, n=7):
 
 
 _NP_TO_CODE = {np.dtype(np.uint8): U8, np.dtype(np.uint16): U16, np.dtype(np.int32): I32,
-               np.dtype(np.float32): F32, np.dtype(np.uint32): U32}
+               np.dtype(np.float32): F32, np.dtype(np.uint32): U32, np.dtype(np.int8): I8, np.dtype(np.int16): I16}

@@ -26,7 +26,7 @@ NPRED = {3: 19, 2: 5}
 CODER_DTYPE = {_lib.CODER_RAW: torch.int32, _lib.CODER_U8: torch.uint8, _lib.CODER_U16: torch.uint16,
                _lib.CODER_U32: torch.uint32}
 NATURAL_CODER = {torch.uint8: _lib.CODER_U8, torch.uint16: _lib.CODER_U16, torch.int32: _lib.CODER_RAW,
-                 torch.uint32: _lib.CODER_U32}
+                 torch.uint32: _lib.CODER_U32, torch.int8: _lib.CODER_U8, torch.int16: _lib.CODER_U16}
 
 
 def _sp(shape, nsp):
@@ -137,7 +137,7 @@ def d_lowres_from_highres(h, nsp):
     sp = _sp(h.shape, nsp)
     out = dev.empty((h.shape[0], *[(s + 1) // 2 for s in sp], *_ch(h.shape, nsp)), h.dtype)
     if _empty_ok(h, out):
-        check(lib.kmp_lowres_from_highres(nsp, dev.dtype_code(h), h.data_ptr(), h.shape[0], _lib.i64x3(sp),
+        check(lib.kmp_lowres_from_highres(nsp, dev.move_code(h), h.data_ptr(), h.shape[0], _lib.i64x3(sp),
                                           _C(h.shape, nsp), out.data_ptr(), dev.stream()), 'lowres_from_highres')
     return out
 
@@ -148,7 +148,7 @@ def d_maps_from_highres(h, nsp):
     outs = [dev.empty((h.shape[0], *[(s // 2 if p else (s + 1) // 2) for s, p in zip(sp, par)], *ch), h.dtype)
             for par in PARITY[nsp]]
     if _empty_ok(h, *outs):
-        check(lib.kmp_maps_from_highres(nsp, dev.dtype_code(h), h.data_ptr(), h.shape[0], _lib.i64x3(sp),
+        check(lib.kmp_maps_from_highres(nsp, dev.move_code(h), h.data_ptr(), h.shape[0], _lib.i64x3(sp),
                                         _C(h.shape, nsp), _lib.ptrs(outs), dev.stream()), 'maps_from_highres')
     return tuple(outs)
 
@@ -157,7 +157,7 @@ def d_targets_from_highres(h, nsp):
     sp = _sp(h.shape, nsp)
     out = dev.empty((h.shape[0], *[(s - 1) // 2 for s in sp], NPRED[nsp], *_ch(h.shape, nsp)), h.dtype)
     if _empty_ok(h, out):
-        check(lib.kmp_targets_from_highres(nsp, dev.dtype_code(h), h.data_ptr(), h.shape[0], _lib.i64x3(sp),
+        check(lib.kmp_targets_from_highres(nsp, dev.move_code(h), h.data_ptr(), h.shape[0], _lib.i64x3(sp),
                                            _C(h.shape, nsp), out.data_ptr(), dev.stream()), 'targets_from_highres')
     return out
 
@@ -168,8 +168,8 @@ def d_copy_box(src, in_off, ext, dst, out_off, nsp):
         return dst
     C = _C(src.shape, nsp)
     _require(C == _C(dst.shape, nsp) and src.shape[0] == dst.shape[0], 'box copy: batch/channel mismatch')
-    check(lib.kmp_copy_box(nsp, dev.dtype_code(src), src.data_ptr(), _lib.i64x3(_sp(src.shape, nsp)),
-                           _lib.i64x3(in_off), dev.dtype_code(dst), dst.data_ptr(), _lib.i64x3(_sp(dst.shape, nsp)),
+    check(lib.kmp_copy_box(nsp, dev.move_code(src), src.data_ptr(), _lib.i64x3(_sp(src.shape, nsp)),
+                           _lib.i64x3(in_off), dev.move_code(dst), dst.data_ptr(), _lib.i64x3(_sp(dst.shape, nsp)),
                            _lib.i64x3(out_off), src.shape[0], C, _lib.i64x3(ext), dev.stream()), 'copy_box')
     return dst
 
@@ -197,7 +197,7 @@ def d_highres_from_lowres_and_maps(lowres, maps, nsp):
         maps[i] = d_cast(m, lowres.dtype, nsp)
     out = dev.empty((lowres.shape[0], *[2 * l - 1 for l in L], *ch), lowres.dtype)
     if _empty_ok(lowres, out):
-        check(lib.kmp_highres_from_lowres_and_maps(nsp, dev.dtype_code(lowres), lowres.data_ptr(), _lib.ptrs(maps),
+        check(lib.kmp_highres_from_lowres_and_maps(nsp, dev.move_code(lowres), lowres.data_ptr(), _lib.ptrs(maps),
                                                    lowres.shape[0], _lib.i64x3(L), _C(lowres.shape, nsp),
                                                    out.data_ptr(), dev.stream()), 'highres_from_lowres_and_maps')
     return out
@@ -210,7 +210,7 @@ def d_features_from_lowres(lowres, padding, nsp):
     _require(all(c >= 0 for c in cells), 'lowres window smaller than the neighbourhood')
     out = dev.empty((lowres.shape[0], *cells, k ** nsp, *_ch(lowres.shape, nsp)), lowres.dtype)
     if _empty_ok(lowres, out):
-        check(lib.kmp_features_from_lowres(nsp, dev.dtype_code(lowres), lowres.data_ptr(), lowres.shape[0],
+        check(lib.kmp_features_from_lowres(nsp, dev.move_code(lowres), lowres.data_ptr(), lowres.shape[0],
                                            _lib.i64x3(S), _C(lowres.shape, nsp), padding, out.data_ptr(),
                                            dev.stream()), 'features_from_lowres')
     return out
@@ -261,7 +261,7 @@ def d_pad(x, lo, hi, mode, nsp):
     out_sp = [s + a + b for s, a, b in zip(sp, lo, hi)]
     out = dev.empty((x.shape[0], *out_sp, *_ch(x.shape, nsp)), x.dtype)
     if _empty_ok(x, out):
-        check(lib.kmp_pad(nsp, dev.dtype_code(x), x.data_ptr(), x.shape[0], _lib.i64x3(sp), _C(x.shape, nsp),
+        check(lib.kmp_pad(nsp, dev.move_code(x), x.data_ptr(), x.shape[0], _lib.i64x3(sp), _C(x.shape, nsp),
                           _lib.i64x3(lo), _lib.i64x3(hi), mode, out.data_ptr(), dev.stream()), 'pad')
     return out
 
@@ -366,7 +366,7 @@ def d_window_from_highres(h, padding, nsp):
     L = [(s + d + 1) // 2 for s, d in zip(sp, highres_dims(h.shape, nsp))]
     out = dev.empty((h.shape[0], *[l + 2 * padding for l in L], *_ch(h.shape, nsp)), h.dtype)
     if _empty_ok(h, out):
-        check(lib.kmp_window_from_highres(nsp, dev.dtype_code(h), h.data_ptr(), h.shape[0], _lib.i64x3(sp),
+        check(lib.kmp_window_from_highres(nsp, dev.move_code(h), h.data_ptr(), h.shape[0], _lib.i64x3(sp),
                                           _C(h.shape, nsp), padding, out.data_ptr(), dev.stream()), 'window')
     return out
 
@@ -376,7 +376,7 @@ def d_window_from_lowres(lo, dims, padding, nsp):
     E = _sp(lo.shape, nsp)
     out = dev.empty((lo.shape[0], *[e + d + 2 * padding for e, d in zip(E, dims)], *_ch(lo.shape, nsp)), lo.dtype)
     if _empty_ok(lo, out):
-        check(lib.kmp_window_from_lowres(nsp, dev.dtype_code(lo), lo.data_ptr(), lo.shape[0], _lib.i64x3(E),
+        check(lib.kmp_window_from_lowres(nsp, dev.move_code(lo), lo.data_ptr(), lo.shape[0], _lib.i64x3(E),
                                          _C(lo.shape, nsp), _lib.i32xn(dims), padding, out.data_ptr(), dev.stream()),
               'window')
     return out

@@ -51,7 +51,21 @@ MAGIC = b'KMPF'
 VERSION = 3  # 2: rice payloads are v2 bundles (packing.py); 3: a LinearPredictor's arith_rev recorded
 _HEAD = struct.Struct('<4sHHQ')
 _NP_NAME = {torch.uint8: 'uint8', torch.uint16: 'uint16', torch.int32: 'int32', torch.uint32: 'uint32',
-            torch.float32: 'float32'}
+            torch.float32: 'float32', torch.int8: 'int8', torch.int16: 'int16'}
+# Signed samples (int8 / int16): the metadata says 'int8' / 'int16' and the bundle stores the coarsest
+# lowres under the signed dtype code, as its own bit pattern (the Rice zigzag reads samples as signed,
+# so small signed values stay small); the maps are the unsigned residuals.  A build from before
+# signed samples knows neither the name nor the code and refuses such a file.
+_SAMPLE_NAMES = frozenset(_NP_NAME.values())
+
+
+def _check_sample_dtype(meta, path):
+    """A file of a sample dtype this build does not know is refused, not misdecoded."""
+    for key in ('sample_dtype', 'lowres_dtype'):
+        name = meta.get(key)
+        if name is not None and name not in _SAMPLE_NAMES:
+            raise ValueError(f'{path}: {key} {name!r} is not a sample dtype this build knows '
+                             f'({", ".join(sorted(_SAMPLE_NAMES))}): read it with the build that wrote it')
 
 
 def _predictor_meta(predictor, padding, ndim, dtype):
@@ -231,6 +245,7 @@ def _read_head(f, path):
         n = int(meta['bundle_bytes'])
     except (ValueError, KeyError, TypeError) as e:
         raise ValueError(f'{path}: corrupt metadata ({e})') from None
+    _check_sample_dtype(meta, path)
     if version == 1 and meta.get('method') != 'planes':
         # version-1 'rice' payloads were the per-array KMPR format, replaced by the v2 bundle;
         # version-1 'planes' payloads are unchanged and still read
@@ -346,8 +361,8 @@ def _auto_levels(shape, ndim, max_levels=4):
 
 def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False):
     """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
-    :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int32
-    raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
+    :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int8 / int16
+    modular on the sign-mapped samples, int32 raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
     reference's single-level ``encode`` (volume/encode_decode.py:30-56) applied to the previous
     level's lowres, so only the coarsest lowres is stored raw -- entropy-code every array and write
     ``path``.  Returns ``{'bytes', 'raw_bytes', 'ratio', 'bits_per_sample', 'levels'}``.

@@ -565,6 +565,9 @@ int kmp_encode_with_predictions_typed(int32_t nsp, int32_t dtype, int32_t coder,
   KMP_REQUIRE(nsp == 2 || nsp == 3, "nsp must be 2 or 3");
   KMP_REQUIRE(highres && shape && preds && lowres_out && maps_out && B >= 0 && C >= 1, "bad argument");
   for (int a = 0; a < nsp; ++a) KMP_REQUIRE(shape[a] >= 2, "spatial dims must be >= 2");
+  // signed samples: sample-dtype or float32 predictions code the same bits mod 2^W (kmp_common.h)
+  if (pred_dtype == dtype) pred_dtype = unsigned_twin(dtype);
+  dtype = unsigned_twin(dtype);
   const Geo g = make_geo_from_highres(nsp, shape);
   CMapPtrs pp{};
   MapPtrs mp{};
@@ -618,6 +621,8 @@ int kmp_decode_with_predictions_typed(int32_t nsp, int32_t dtype, int32_t coder,
     KMP_REQUIRE(dims[a] == 0 || dims[a] == 1, "dims must be 0 or 1");
     KMP_REQUIRE(shape[a] >= 1 && shape[a] + dims[a] >= 2, "lowres too small");
   }
+  if (pred_dtype == dtype) pred_dtype = unsigned_twin(dtype);  // signed samples: as the encode
+  dtype = unsigned_twin(dtype);
   const Geo g = make_geo_from_lowres(nsp, shape, dims);
   CMapPtrs pp{}, mp{};
   KMP_REQUIRE(bind_maps(nsp, preds, pp) && bind_maps(nsp, maps, mp), "null map pointer");

@@ -12,6 +12,8 @@ template <> constexpr int dtype_code<uint16_t>() { return KMP_U16; }
 template <> constexpr int dtype_code<int32_t>() { return KMP_I32; }
 template <> constexpr int dtype_code<uint32_t>() { return KMP_U32; }
 template <> constexpr int dtype_code<float>() { return KMP_F32; }
+template <> constexpr int dtype_code<i8s>() { return KMP_I8; }
+template <> constexpr int dtype_code<i16s>() { return KMP_I16; }
 
 int64_t generic_workspace_bytes(int dtype, int nsp, const Geo& g, int64_t B, int64_t C, const kmp_predictor* pred);
 
@@ -38,18 +40,22 @@ struct CodecCall {
 };
 
 // The coder of a request is the natural coder of its sample type (the front door admits no other
-// pair): (u8, U8), (u16, U16), (i32, RAW), (u32, U32).
+// pair): (u8, U8), (u16, U16), (i32, RAW), (u32, U32), and the signed (i8, U8), (i16, U16), whose
+// residuals are the unsigned type's (Signed, kmp_common.h).
 template <typename T> struct natural_coder;
 template <> struct natural_coder<uint8_t> { static constexpr int value = KMP_CODER_U8; };
 template <> struct natural_coder<uint16_t> { static constexpr int value = KMP_CODER_U16; };
 template <> struct natural_coder<int32_t> { static constexpr int value = KMP_CODER_RAW; };
 template <> struct natural_coder<uint32_t> { static constexpr int value = KMP_CODER_U32; };
+template <> struct natural_coder<i8s> { static constexpr int value = KMP_CODER_U8; };
+template <> struct natural_coder<i16s> { static constexpr int value = KMP_CODER_U16; };
 
 // Kernel families, one per kmp_codec_<family>.hip.  Each returns KMP_ERR_UNSUPPORTED (without
 // touching anything) when the request is not eligible, and knows nothing of the others: the order
 // they are tried in is the table next to codec_encode / codec_decode (kmp_codec.hip).  The one-pass
 // families are instantiated for uint8_t / uint16_t, wave3d32 for int32_t / uint32_t; the generic
-// two-pass path for all four, and it takes every request.
+// two-pass path for all four, and it takes every request.  Signed samples (i8s / i16s) are served by
+// wave3d, wave2d and the generic path only: their lists in the table name no other family.
 template <typename T, bool DEC> int try_wave3d(const CodecCall<T, DEC>& c);
 template <typename T, bool DEC> int try_wave3d32(const CodecCall<T, DEC>& c);
 template <typename T, bool DEC> int try_wave3dp(const CodecCall<T, DEC>& c);
@@ -67,7 +73,8 @@ template <typename T, bool DEC> int try_generic(const CodecCall<T, DEC>& c);
   template int F<T, false>(const CodecCall<T, false>&); \
   template int F<T, true>(const CodecCall<T, true>&);
 #define KMP_INST_FAMILY_U8_U16(F) KMP_INST_FAMILY(F, uint8_t) KMP_INST_FAMILY(F, uint16_t)
-#define KMP_FOR_SAMPLE_TYPES(M) M(uint8_t) M(uint16_t) M(int32_t) M(uint32_t)
+#define KMP_INST_FAMILY_SIGNED(F) KMP_INST_FAMILY(F, i8s) KMP_INST_FAMILY(F, i16s)
+#define KMP_FOR_SAMPLE_TYPES(M) M(uint8_t) M(uint16_t) M(int32_t) M(uint32_t) M(i8s) M(i16s)
 
 // ------------------------------------------------------------------------------------------
 // Host checks and argument filling the families share

@@ -11,7 +11,9 @@ static int dispatch_natural(int dtype, int coder, F&& f) {
   if (dtype == KMP_U16 && coder == natural_coder<uint16_t>::value) return f(uint16_t{});
   if (dtype == KMP_I32 && coder == natural_coder<int32_t>::value) return f(int32_t{});
   if (dtype == KMP_U32 && coder == natural_coder<uint32_t>::value) return f(uint32_t{});
-  return fail(KMP_ERR_UNSUPPORTED, "fused codec supports (uint8, U8), (uint16, U16), (int32, RAW), (uint32, U32); got dtype " +
+  if (dtype == KMP_I8 && coder == natural_coder<i8s>::value) return f(i8s{});
+  if (dtype == KMP_I16 && coder == natural_coder<i16s>::value) return f(i16s{});
+  return fail(KMP_ERR_UNSUPPORTED, "fused codec supports (uint8, U8), (uint16, U16), (int32, RAW), (uint32, U32), (int8, U8), (int16, U16); got dtype " +
                                        std::to_string(dtype) + " coder " + std::to_string(coder));
 }
 
@@ -33,6 +35,12 @@ static int serve(const CodecCall<T, DEC>& c) {
   if constexpr (sizeof(T) == 4) {
     static constexpr Try volume[] = {try_wave3d32<T, DEC>, try_generic<T, DEC>, nullptr};
     static constexpr Try image[] = {try_generic<T, DEC>, nullptr};
+    family = c.nsp == 3 ? volume : image;
+  } else if constexpr (sample_sign<T> != 0) {
+    // signed samples: the kernels that apply the sign map (DESIGN.md "Signed samples"); the others
+    // are not instantiated for them, so everything else is the generic path's
+    static constexpr Try volume[] = {try_wave3d<T, DEC>, try_generic<T, DEC>, nullptr};  // mean p = 0 | anything
+    static constexpr Try image[] = {try_wave2d<T, DEC>, try_generic<T, DEC>, nullptr};   // mean p = 0 | anything
     family = c.nsp == 3 ? volume : image;
   } else {
     static constexpr Try volume[] = {
@@ -67,7 +75,8 @@ static int check_predictor(const kmp_predictor* pred, int dtype) {
               "unknown predictor kind");
   if (pred->kind != KMP_PRED_MEAN) KMP_REQUIRE(pred->weights && pred->bias, "linear predictor needs weights and bias");
   if (pred->kind == KMP_PRED_LINEAR_MFMA)
-    KMP_REQUIRE(dtype == KMP_U8 || dtype == KMP_U16, "the matrix-core LinearPredictor takes uint8 / uint16 samples");
+    KMP_REQUIRE(dtype == KMP_U8 || dtype == KMP_U16,
+                "the matrix-core LinearPredictor takes uint8 / uint16 samples (signed int8 / int16: use KMP_PRED_LINEAR)");
   return KMP_OK;
 }
 

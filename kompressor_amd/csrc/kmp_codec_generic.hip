@@ -178,5 +178,6 @@ KMP_INST_FAMILY(try_generic, uint8_t)
 KMP_INST_FAMILY(try_generic, uint16_t)
 KMP_INST_FAMILY(try_generic, int32_t)
 KMP_INST_FAMILY(try_generic, uint32_t)
+KMP_INST_FAMILY_SIGNED(try_generic)
 
 }  // namespace kmp

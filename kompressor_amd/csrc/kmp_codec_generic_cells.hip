@@ -169,7 +169,9 @@ int run_predictor(const T* src, const Src& s, const Geo& g, int nsp, int64_t B, 
     const bool i32 = fits32(g, B, C, 1);
     const int p = pred->padding, kk = 2 * p + 2;
     const int64_t nn = (nsp == 3 ? kk : 1) * (int64_t)kk * kk;
-    const int64_t top = std::is_same<T, uint8_t>::value ? 255 : (std::is_same<T, uint16_t>::value ? 65535 : -1);
+    // (signed samples are summed as M(x), Signed in kmp_common.h: the unsigned type's range)
+    using TM = typename sample_traits<T>::mapped;
+    const int64_t top = std::is_same<TM, uint8_t>::value ? 255 : (std::is_same<TM, uint16_t>::value ? 65535 : -1);
     if (i32 && p <= 3) {  // cell_mean_row_kernel: exact integer sums when they are, else in-order floats
       const bool exact = top > 0 && nn * top < ((int64_t)1 << 24);
       const int64_t ext_q[3] = {cf.ext[0], cf.ext[1], ceil_div(cf.ext[2], (int64_t)kMeanR)};

@@ -15,7 +15,9 @@ typedef uint32_t g32a1 __attribute__((aligned(1)));
 typedef uint8_t g8x4 __attribute__((ext_vector_type(4)));
 typedef uint8_t g8x4a1 __attribute__((ext_vector_type(4), aligned(1)));
 
-// N consecutive samples (N x sizeof(T) a multiple of 4 bytes) as unaligned dword vector accesses
+// N consecutive samples (N x sizeof(T) a multiple of 4 bytes) as unaligned dword vector accesses.
+// The values are the samples as numbers: M(x) for signed T (Signed, kmp_common.h), which these
+// word-level accesses apply themselves (wv::smap: one xor per dword, nothing for any other type).
 template <typename T, int N>
 __device__ __forceinline__ void g_loadn(const T* p, uint32_t (&v)[N]) {
   constexpr int NW = N * (int)sizeof(T) / 4;
@@ -36,6 +38,8 @@ __device__ __forceinline__ void g_loadn(const T* p, uint32_t (&v)[N]) {
   constexpr int PER = 4 / (int)(sizeof(T) < 4 ? sizeof(T) : 4);
   constexpr uint32_t MASK = sizeof(T) == 1 ? 0xffu : (sizeof(T) == 2 ? 0xffffu : 0xffffffffu);
 #pragma unroll
+  for (int i = 0; i < NW; ++i) w[i] = wv::smap<T>(w[i]);  // signed samples: one xor per dword
+#pragma unroll
   for (int e = 0; e < N; ++e) v[e] = (w[e / PER] >> (8 * sizeof(T) * (e % PER))) & MASK;
 }
 template <typename T, int N>
@@ -49,6 +53,8 @@ __device__ __forceinline__ void g_storen(T* p, const uint32_t (&v)[N]) {
   for (int i = 0; i < NW; ++i) w[i] = 0u;
 #pragma unroll
   for (int e = 0; e < N; ++e) w[e / PER] |= (v[e] & MASK) << (8 * sizeof(T) * (e % PER));
+#pragma unroll
+  for (int i = 0; i < NW; ++i) w[i] = wv::smap<T>(w[i]);  // signed samples: one xor per dword
   char* c = (char*)p;
   constexpr int N4 = NW / 4 * 4;
 #pragma unroll
@@ -84,6 +90,9 @@ __global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restric
   }
   using I = int32_t;
   using TO = typename coder_out<CODER>::type;
+  // the numbers of the samples (signed samples: M(x), Signed in kmp_common.h; any other type: T
+  // itself): cells and samples are converted once where they are loaded and kept as numbers
+  using TM = typename sample_traits<T>::mapped;
   constexpr int NM = NSP == 3 ? 7 : 3;
   constexpr int NZ = NSP == 3 ? 2 : 1;
   constexpr int NH = 8 * CC, NO = 4 * CC;  // samples of a highres row segment / of an output group
@@ -107,7 +116,7 @@ __global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restric
     // ---- the cells around the 4 outputs: (oz - dz, oy - dy, ox0 - 1 + j), j = 0..4 ----
     const I cbase = b * cb + oz * cz + oy * cy + ox0 * CC;  // cell (oz, oy, ox0), channel 0
     bool cv[2][2][5];
-    T cm[2][2][5][CC];
+    TM cm[2][2][5][CC];
 #pragma unroll
     for (int dz = 0; dz < 2; ++dz)
 #pragma unroll
@@ -120,12 +129,12 @@ __global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restric
           cv[dz][dy][j] = rowok && x >= 0 && x < (I)g.Lc[2];
 #pragma unroll
           for (int ch = 0; ch < CC; ++ch)
-            if (!PERCH) cm[dz][dy][j][ch] = cv[dz][dy][j] ? cells[cbase - dz * cz - dy * cy + (j - 1) * CC + ch] : T(0);
+            if (!PERCH) cm[dz][dy][j][ch] = cv[dz][dy][j] ? (TM)cells[cbase - dz * cz - dy * cy + (j - 1) * CC + ch] : TM(0);
         }
       }
     // map k's contribution channel kch of the cell (oz - dz, oy - dy, ox0 + i - dx), sample channel ch
     // FK > 0: the cells (oy - dy, ox0 - 1 + j), channels kch, computed here
-    T pc[FK > 0 ? 2 : 1][FK > 0 ? 5 : 1][FKO];
+    TM pc[FK > 0 ? 2 : 1][FK > 0 ? 5 : 1][FKO];
     if constexpr (FK > 0) {
       constexpr int NRW = FK + 1, NCL = FK + 4;  // node patch: rows oy - 1 - p .., cols ox0 - 1 - p ..
       const I sr = DEC ? (I)g.E[2] : (I)g.n[2];
@@ -156,12 +165,12 @@ __global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restric
               for (int k = 0; k < FKO; ++k) acc[k] = __builtin_fmaf(fv, wl[(fy * FK + fx) * FKO + k], acc[k]);
             }
 #pragma unroll
-          for (int k = 0; k < FKO; ++k) pc[dy][j][k] = lin_cast_t<T>(acc[k]);
+          for (int k = 0; k < FKO; ++k) pc[dy][j][k] = lin_cast_t<TM>(acc[k]);
         }
     }
-    auto cell = [&](int i, int dz, int dy, int dx, int kch, int ch) -> T {
+    auto cell = [&](int i, int dz, int dy, int dx, int kch, int ch) -> TM {
       if constexpr (FK > 0) return pc[dy][i + 1 - dx][kch];
-      else if constexpr (PERCH) return cells[cbase - dz * cz - dy * cy + (i - dx) * CC + ch + (I)kch * kp];
+      else if constexpr (PERCH) return (TM)cells[cbase - dz * cz - dy * cy + (i - dx) * CC + ch + (I)kch * kp];
       else return cm[dz][dy][i + 1 - dx][ch];
     };
     auto pred = [&](int k, int i, int ch) -> uint32_t {
@@ -180,7 +189,7 @@ __global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restric
       }
       if (cnt == 4) sacc *= 0.25f;
       else if (cnt == 2) sacc *= 0.5f;
-      return (uint32_t)to_i32(gcast<T>(sacc));
+      return (uint32_t)to_i32(gcast<TM>(sacc));
     };
     if constexpr (!DEC) {
       // ---- encode: the 8 x CC samples of each of the 2^d highres rows, then lowres + maps ----
@@ -226,7 +235,7 @@ __global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restric
 #pragma unroll
           for (int ch = 0; ch < CC; ++ch)
             ov[i * CC + ch] = (uint32_t)code_encode<CODER>((int32_t)pred(k, i, ch),
-                                                           to_i32((T)hv[NSP == 3 ? p0 : 0][p1][(2 * i + p2) * CC + ch]));
+                                                           to_i32((TM)hv[NSP == 3 ? p0 : 0][p1][(2 * i + p2) * CC + ch]));
         TO* mp = (TO*)omaps.p[k] + (((b * e0 + oz) * e1 + oy) * e2 + ox0) * CC;
         if (n == 4) g_storen<TO, NO>(mp, ov);
         else
@@ -281,7 +290,7 @@ __global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restric
 #pragma unroll
           for (int ch = 0; ch < CC; ++ch)
             hv[NSP == 3 ? p0 : 0][p1][2 * i + p2][ch] =
-                (uint32_t)(T)code_decode<CODER>((int32_t)pred(k, i, ch), (int32_t)(TO)mv[i * CC + ch]);
+                (uint32_t)(TM)code_decode<CODER>((int32_t)pred(k, i, ch), (int32_t)(TO)mv[i * CC + ch]);
           hok[NSP == 3 ? p0 : 0][p1][2 * i + p2] = i < n;
         }
       }

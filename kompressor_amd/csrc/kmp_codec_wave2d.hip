@@ -100,6 +100,15 @@ __device__ __forceinline__ void wave2d_body(const W2& a, int vblk) {
     if (live && vy1) o0 = ld16(hin + (2 * Yc + 1) * a.W + hx);
   }
 
+  // signed samples: M on the sample-domain registers just loaded (the decode's residual rows stay
+  // as they are); both predictor arms below then run the unsigned arithmetic.  Nothing for unsigned T
+  if constexpr (sample_sign<T> != 0) {
+    own = smap<T>(own);
+    halo = smap<T>(halo);
+    hdn = smap<T>(hdn);
+    if constexpr (!DEC) o0 = smap<T>(o0);
+  }
+
   // ---- 2x2 node sums: row Y, and on the wave's first row also row Y-1 ----
   uint32_t n[VX], nh[VX], nd[VX];
 #pragma unroll
@@ -217,7 +226,7 @@ __device__ __forceinline__ void wave2d_body(const W2& a, int vblk) {
       res[1][i] = (el16<T>(own, 2 * i + 1) - pred[1][i]) & MASK;  // UD (0,1)
       res[2][i] = (el16<T>(o0, 2 * i + 1) - pred[2][i]) & MASK;   // C  (1,1)
     }
-    stp8<STC>((T*)a.lo_out + m_ud, pack8<T, VX>(lov));
+    stp8<STC>((T*)a.lo_out + m_ud, smap<T>(pack8<T, VX>(lov)));  // lowres: back to the caller's type
     if (vy1) stp8<STC>((T*)a.maps.p[0] + m_lr, pack8<T, VX>(res[0]));
     stp8<STC>((T*)a.maps.p[1] + m_ud, pack8<T, VX>(res[1]));
     if (vy1) stp8<STC>((T*)a.maps.p[2] + m_lr, pack8<T, VX>(res[2]));
@@ -228,8 +237,9 @@ __device__ __forceinline__ void wave2d_body(const W2& a, int vblk) {
 #pragma unroll
       for (int i = 0; i < VX; ++i) dv[k][i] = (pred[k][i] + el8<T>(mv[k], i)) & MASK;
     T* h0 = hout + 2 * Yc * a.W + hx;
-    st16(h0, pack16<T, VX>(n, dv[1]));                    // row 2Y: lowres | UD
-    if (vy1) st16(h0 + a.W, pack16<T, VX>(dv[0], dv[2]));  // row 2Y+1: LR | C
+    // (signed samples: highres goes back to the caller's type)
+    st16(h0, smap<T>(pack16<T, VX>(n, dv[1])));                    // row 2Y: lowres | UD
+    if (vy1) st16(h0 + a.W, smap<T>(pack16<T, VX>(dv[0], dv[2])));  // row 2Y+1: LR | C
   }
 }
 
@@ -443,5 +453,6 @@ int try_wave2d(const CodecCall<T, DEC>& c) {
 }
 
 KMP_INST_FAMILY_U8_U16(try_wave2d)
+KMP_INST_FAMILY_SIGNED(try_wave2d)
 
 }  // namespace kmp

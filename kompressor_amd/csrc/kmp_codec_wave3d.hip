@@ -240,6 +240,25 @@ __device__ __forceinline__ void wave3d_plane_body(const W3& a, int vblk) {
     }
   }
 
+  // signed samples: M on every sample-domain register just loaded (highres in an encode, lowres
+  // nodes in a decode; the decode's residual rows stay as they are); nothing for unsigned T
+  if constexpr (sample_sign<T> != 0) {
+#pragma unroll
+    for (int t = 0; t < PL + 2; ++t) {
+      N[t].own = smap<T>(N[t].own);
+      N[t].halo = smap<T>(N[t].halo);
+      N[t].dn = smap<T>(N[t].dn);
+    }
+    if constexpr (!DEC) {
+#pragma unroll
+      for (int u = 0; u < PL; ++u) {
+        O[u].e1 = smap<T>(O[u].e1);
+        O[u].o0 = smap<T>(O[u].o0);
+        O[u].o1 = smap<T>(O[u].o1);
+      }
+    }
+  }
+
   // ---- 2x2 node sums per node plane (rows Y and, on the wave's first row, Y-1) ----
   uint32_t S[PL + 2][VX], Su[PL + 2][VX];
 #pragma unroll
@@ -344,7 +363,7 @@ __device__ __forceinline__ void wave3d_plane_body(const W3& a, int vblk) {
       // one uniform branch around the plane's 8 stores, so that each flavour is straight-line code
       auto put = [&](auto cached) __attribute__((always_inline)) {
         constexpr bool STC = decltype(cached)::value;
-        stp8<STC>(lp, pack8<T, VX>(lov));
+        stp8<STC>(lp, smap<T>(pack8<T, VX>(lov)));  // lowres: back to the caller's type
 #pragma unroll
         for (int k = 0; k < 7; ++k) {
           int par[3];
@@ -369,12 +388,12 @@ __device__ __forceinline__ void wave3d_plane_body(const W3& a, int vblk) {
         for (int i = 0; i < VX; ++i) dv[k][i] = (pred[k][i] + el8<T>(Oc.mv[k], i)) & MASK;
       T* h0 = hout + 2 * c * hplane + ho_own;
       KMP_SPAN((T*)a.hi_out, h0 + (vz1 ? hplane : 0) + (vy1 ? a.W : 0), 2 * VX, a.nB * a.D * hplane);
-      st16(h0, pack16<T, VX>(own, dv[6]));
-      if (vy1) st16(h0 + a.W, pack16<T, VX>(dv[5], dv[2]));
+      st16(h0, smap<T>(pack16<T, VX>(own, dv[6])));  // highres: back to the caller's type
+      if (vy1) st16(h0 + a.W, smap<T>(pack16<T, VX>(dv[5], dv[2])));
       if (vz1) {
         T* h1 = h0 + hplane;
-        st16(h1, pack16<T, VX>(dv[4], dv[1]));
-        if (vy1) st16(h1 + a.W, pack16<T, VX>(dv[0], dv[3]));
+        st16(h1, smap<T>(pack16<T, VX>(dv[4], dv[1])));
+        if (vy1) st16(h1 + a.W, smap<T>(pack16<T, VX>(dv[0], dv[3])));
       }
     }
   }
@@ -489,5 +508,6 @@ int try_wave3d(const CodecCall<T, DEC>& c) {
 }
 
 KMP_INST_FAMILY_U8_U16(try_wave3d)
+KMP_INST_FAMILY_SIGNED(try_wave3d)
 
 }  // namespace kmp

@@ -66,17 +66,44 @@ int opt(Opt id, int dflt);
 // ------------------------------------------------------------------------------------------
 // dtype traits
 // ------------------------------------------------------------------------------------------
+// Signed 8- / 16-bit samples (KMP_I8 / KMP_I16).  Storage is the caller's two's-complement bit
+// pattern; every arithmetic view of a sample is M(x) = x ^ signbit, the order-preserving map onto the
+// unsigned type of the same width (DESIGN.md "Signed samples").  A kernel templated on its sample
+// type gets the map from the conversions alone: reading a Signed<U> as a number gives M(x), and
+// constructing one from a number stores M^-1 of it, so predictions, means and casts run on exactly
+// the unsigned arithmetic.  Kernels that move packed registers apply sample_sign<T> themselves.
+template <typename U>
+struct Signed {
+  static constexpr U kSign = (U)(U(1) << (8 * sizeof(U) - 1));
+  U raw;
+  Signed() = default;
+  __host__ __device__ constexpr Signed(U mapped) : raw((U)(mapped ^ kSign)) {}
+  __host__ __device__ constexpr operator U() const { return (U)(raw ^ kSign); }
+};
+using i8s = Signed<uint8_t>;
+using i16s = Signed<uint16_t>;
+
+// the sign bit M flips (0: the type is not mapped), and the unsigned type arithmetic runs in
+template <typename T> struct sample_traits { static constexpr uint32_t sign = 0u; using mapped = T; };
+template <typename U> struct sample_traits<Signed<U>> { static constexpr uint32_t sign = Signed<U>::kSign; using mapped = U; };
+template <typename T> constexpr uint32_t sample_sign = sample_traits<T>::sign;
+// 8- / 16-bit integer samples, mapped or not: the types with exact f32 sums and the saturating cast
+template <typename T> constexpr bool is_small_sample =
+    std::is_same<typename sample_traits<T>::mapped, uint8_t>::value || std::is_same<typename sample_traits<T>::mapped, uint16_t>::value;
+
 template <int DT> struct dtype_of;
 template <> struct dtype_of<KMP_U8> { using type = uint8_t; };
 template <> struct dtype_of<KMP_U16> { using type = uint16_t; };
 template <> struct dtype_of<KMP_I32> { using type = int32_t; };
 template <> struct dtype_of<KMP_F32> { using type = float; };
 template <> struct dtype_of<KMP_U32> { using type = uint32_t; };
+template <> struct dtype_of<KMP_I8> { using type = i8s; };
+template <> struct dtype_of<KMP_I16> { using type = i16s; };
 
 inline int dtype_size(int dt) {
   switch (dt) {
-    case KMP_U8: return 1;
-    case KMP_U16: return 2;
+    case KMP_U8: case KMP_I8: return 1;
+    case KMP_U16: case KMP_I16: return 2;
     case KMP_I32: case KMP_F32: case KMP_U32: return 4;
     default: return 0;
   }
@@ -93,11 +120,29 @@ int dispatch_int_dtype(int dt, F&& f) {  // integer sample dtypes (highres / low
     default: return fail(KMP_ERR_ARG, "unsupported sample dtype " + std::to_string(dt));
   }
 }
+// integer sample dtypes of the launches that do arithmetic on samples: the signed ones too (the
+// data-movement primitives take the same-width unsigned code instead)
+template <typename F>
+int dispatch_sample_dtype(int dt, F&& f) {
+  if (dt == KMP_I8) return f(i8s{});
+  if (dt == KMP_I16) return f(i16s{});
+  return dispatch_int_dtype(dt, f);
+}
+template <typename F>
+int dispatch_any_sample_dtype(int dt, F&& f) {
+  if (dt == KMP_F32) return f(float{});
+  return dispatch_sample_dtype(dt, f);
+}
 template <typename F>
 int dispatch_any_dtype(int dt, F&& f) {
   if (dt == KMP_F32) return f(float{});
   return dispatch_int_dtype(dt, f);
 }
+
+// The same-width unsigned code of a signed sample dtype (any other code: itself).  The coders work
+// mod 2^W, where M cancels: (M(gt) - M(pred)) mod 2^W == (gt - pred) mod 2^W, so the stand-alone
+// coder launches run the unsigned kernels on the same bits.
+inline int unsigned_twin(int dt) { return dt == KMP_I8 ? KMP_U8 : (dt == KMP_I16 ? KMP_U16 : dt); }
 
 // ------------------------------------------------------------------------------------------
 // Reference arithmetic restated on device
@@ -109,6 +154,8 @@ template <typename T>
 __host__ __device__ __forceinline__ T cast_f32(float v) {
   if constexpr (std::is_same<T, float>::value) {
     return v;
+  } else if constexpr (sample_sign<T> != 0) {
+    return T(cast_f32<typename sample_traits<T>::mapped>(v));  // signed samples: the cast in the mapped domain
   } else {
     constexpr double lo = (double)std::numeric_limits<T>::min();
     constexpr double hi = (double)std::numeric_limits<T>::max();

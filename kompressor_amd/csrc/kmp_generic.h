@@ -61,7 +61,7 @@ __device__ __forceinline__ void unflat_i(int64_t t, const Flat& F, const int64_t
 // (cvt_sat, kmp_wave.h), the exact restatement otherwise
 template <typename T>
 __device__ __forceinline__ T gcast(float v) {
-  if constexpr (std::is_same<T, uint8_t>::value || std::is_same<T, uint16_t>::value) return (T)wv::cvt_sat<T>(v);
+  if constexpr (is_small_sample<T>) return (T)wv::cvt_sat<T>(v);
   else return cast_f32<T>(v);
 }
 

@@ -502,8 +502,14 @@ __device__ __forceinline__ I node_off(const LinSrc& s, int64_t j, int a) {
 
 // R consecutive samples as one (unaligned) store
 template <typename T, int R>
-__device__ __forceinline__ void store_run(T* p, const T (&v)[R]) {
+__device__ __forceinline__ void store_run(T* p, const T (&tv)[R]) {
   static_assert(R == 4, "store_run: 4 samples");
+  uint32_t v[R];  // the stored bit patterns (signed samples: not their numeric view M(x))
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if constexpr (sample_sign<T> != 0) v[r] = tv[r].raw;
+    else v[r] = (uint32_t)tv[r];
+  }
   if constexpr (sizeof(T) == 1) {
     typedef uint32_t u32a1 __attribute__((aligned(1)));
     *(u32a1*)p = (uint32_t)v[0] | ((uint32_t)v[1] << 8) | ((uint32_t)v[2] << 16) | ((uint32_t)v[3] << 24);
@@ -753,6 +759,8 @@ KMP_INSTL(uint8_t)
 KMP_INSTL(uint16_t)
 KMP_INSTL(int32_t)
 KMP_INSTL(uint32_t)
+KMP_INSTL(i8s)
+KMP_INSTL(i16s)
 
 }  // namespace kmp
 
@@ -796,7 +804,7 @@ static int linear_predict(int kind, int32_t nsp, int32_t dtype, const void* padd
     s.Lc[a] = cells;
   }
   s.mult = 0;
-  return dispatch_int_dtype(dtype, [&](auto tag) {
+  return dispatch_sample_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
     return launch_linear<T>((const T*)padded_lowres, s, nsp, padding, B, C, weights, bias, (T*)preds_out, preds_f32,
                             (hipStream_t)stream, kind);

@@ -223,7 +223,7 @@ __global__ void __launch_bounds__(kThreads) maps_from_predictions_lds_kernel(
 template <typename T, bool MEANS>
 static int aggregate_elements(const char* name, int nsp, const T* src, int64_t B, const Ext3& cells, int64_t C,
                               const MapPtrs& outs, int64_t total, bool small, bool shifts, hipStream_t stream) {
-  if constexpr (std::is_same<T, uint8_t>::value || std::is_same<T, uint16_t>::value) {
+  if constexpr (is_small_sample<T>) {
     if (shifts) {
       auto kern = nsp == 3 ? aggregate_maps_int_kernel<T, 3, MEANS> : aggregate_maps_int_kernel<T, 2, MEANS>;
       kern<<<grid_for(total), kThreads, 0, stream>>>(src, (int32_t)cells.e[0], (int32_t)cells.e[1], (int32_t)cells.e[2],
@@ -241,7 +241,7 @@ static int aggregate_elements(const char* name, int nsp, const T* src, int64_t B
 
 int launch_maps_from_cell_means(int nsp, int dtype, const void* cm, int64_t B, const Ext3& cells, int64_t C,
                                 const MapPtrs& outs, int64_t total, bool small, hipStream_t stream) {
-  return dispatch_int_dtype(dtype, [&](auto tag) {
+  return dispatch_sample_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
     return aggregate_elements<T, true>("mean_predict_maps", nsp, (const T*)cm, B, cells, C, outs, total, small,
                                        C == 1 && total < ((int64_t)1 << 31), stream);
@@ -264,7 +264,7 @@ int kmp_maps_from_predictions(int32_t nsp, int32_t dtype, const void* preds, int
   int64_t total = B * C;
   for (int a = 3 - nsp; a < 3; ++a) total *= ce.e[a] + 1;
   if (total == 0) return KMP_OK;
-  return dispatch_any_dtype(dtype, [&](auto tag) {
+  return dispatch_any_sample_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
     const int K = nsp == 3 ? 19 : 5;
     const bool small = fits32({vol(B, ce, C) * K, total});

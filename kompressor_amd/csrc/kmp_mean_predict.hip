@@ -637,7 +637,8 @@ static int mean_predict_maps_impl(int32_t nsp, int32_t dtype, int32_t out_dtype,
     r.total *= r.S.e[a] - 2 * padding;
   }
   if (r.total == 0) return KMP_OK;
-  return dispatch_int_dtype(dtype, [&](auto tag) {
+  // (signed samples, Signed in kmp_common.h, take the element pair: the LDS kernels read packed words)
+  return dispatch_sample_dtype(dtype, [&](auto tag) {
     using T = decltype(tag);
     if constexpr (std::is_same<T, uint8_t>::value || std::is_same<T, uint16_t>::value) {
       for (auto family : {try_p0x8<T>, try_plane<T>})

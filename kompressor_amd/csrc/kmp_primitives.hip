@@ -631,6 +631,8 @@ int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* p
   if (n == 0) return KMP_OK;
   KMP_REQUIRE(pred && x && out, "null pointer");
   hipStream_t s = (hipStream_t)stream;
+  pred_dtype = unsigned_twin(pred_dtype);  // signed samples: the same bits mod 2^W (kmp_common.h)
+  x_dtype = unsigned_twin(x_dtype);
   auto launch = [&](auto dir_c, auto coder_c) {
     constexpr int DIR = decltype(dir_c)::value;
     constexpr int CODER = decltype(coder_c)::value;

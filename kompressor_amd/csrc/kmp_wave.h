@@ -40,6 +40,26 @@ __device__ __forceinline__ void stp8(void* p, uint2 v) {
   else st8(p, v);
 }
 
+// The sign map of signed samples (Signed, kmp_common.h) on packed registers: one xor per dword flips
+// the sign bit of every sample in it, M on a load and M^-1 on a store (the map is its own inverse).
+// Nothing for the unsigned types, whose kernels must not change.
+template <typename T>
+__device__ __forceinline__ uint32_t smap(uint32_t w) {
+  constexpr uint32_t s = sample_sign<T> * (sizeof(T) == 2 ? 0x00010001u : 0x01010101u);
+  if constexpr (s != 0) return w ^ s;
+  else return w;
+}
+template <typename T>
+__device__ __forceinline__ uint4 smap(const uint4& v) {
+  if constexpr (sample_sign<T> != 0) return make_uint4(smap<T>(v.x), smap<T>(v.y), smap<T>(v.z), smap<T>(v.w));
+  else return v;
+}
+template <typename T>
+__device__ __forceinline__ uint2 smap(const uint2& v) {
+  if constexpr (sample_sign<T> != 0) return make_uint2(smap<T>(v.x), smap<T>(v.y));
+  else return v;
+}
+
 template <typename T>
 __device__ __forceinline__ uint32_t el16(const uint4& v, int e) {  // element e of 16 bytes
   const uint32_t w[4] = {v.x, v.y, v.z, v.w};

@@ -99,7 +99,9 @@ class _Plan:
         self.ws = dev.empty((int(lib.kmp_pack_workspace_bytes(self.n)),), torch.uint8)
         self.hlen = _HEAD.size + 8 * t.dim()
         self.side = torch.zeros((_pad8(nb),), dtype=torch.uint8, device='cuda')  # widths, padded to 8 bytes
-        check(lib.kmp_pack_plan(self.code, t.data_ptr(), self.n, self.side.data_ptr(), self.ws.data_ptr(),
+        # (the header records the array's own dtype code; the packers move bits, so signed arrays go
+        # under the same-width unsigned code: dev.bits_code)
+        check(lib.kmp_pack_plan(dev.bits_code(self.code), t.data_ptr(), self.n, self.side.data_ptr(), self.ws.data_ptr(),
                                 dev.stream()), 'pack')
         self.magic, self.unit = ARRAY_MAGIC, 8
         self.poff = self.hlen + self.side.numel()
@@ -119,7 +121,7 @@ class _Plan:
         base = dst.data_ptr()
         check(lib.kmp_pack_header(base, head, len(head), used, dst.numel(), None, 0, -1, dev.stream()), 'pack')
         dst[self.hlen:self.poff].copy_(self.side)
-        check(lib.kmp_pack(self.code, t.data_ptr(), self.n, self.side.data_ptr(), self.ws.data_ptr(),
+        check(lib.kmp_pack(dev.bits_code(self.code), t.data_ptr(), self.n, self.side.data_ptr(), self.ws.data_ptr(),
                            base + self.poff, dev.stream()), 'pack')
 
 
@@ -181,7 +183,7 @@ def _prepare(b, h):
     ws = h['ws'] = dev.empty((int(lib.kmp_pack_workspace_bytes(n)),), torch.uint8)
     widths = h['widths'] = b[woff:woff + nb]
     check(lib.kmp_unpack_plan(widths.data_ptr(), n, ws.data_ptr(), dev.stream()), 'unpack')
-    check(lib.kmp_unpack_check(0, h['code'], widths.data_ptr(), None, n, ws.data_ptr(), dev.stream()), 'unpack')
+    check(lib.kmp_unpack_check(0, dev.bits_code(h['code']), widths.data_ptr(), None, n, ws.data_ptr(), dev.stream()), 'unpack')
     # [payload words the stored block sizes add up to, blocks with impossible side information]
     # (kmp_unpack_check: widths past W)
     off = int(lib.kmp_pack_total_offset(n))
@@ -192,7 +194,7 @@ def _run_unpack(b, h):
     if h['n'] == 0:
         return h['out']
     n, code, ws, out = h['n'], h['code'], h['ws'], h['out']
-    check(lib.kmp_unpack(code, b.data_ptr() + h['poff'], n, h['widths'].data_ptr(), ws.data_ptr(),
+    check(lib.kmp_unpack(dev.bits_code(code), b.data_ptr() + h['poff'], n, h['widths'].data_ptr(), ws.data_ptr(),
                          out.data_ptr(), dev.stream()), 'unpack')
     return out
 
@@ -321,7 +323,7 @@ def _rice_enc_plan(ts, dims):
     runs = []
     tile_begin = 0
     for first, count in _runs(ts):
-        runs.append((first, count, tile_begin, dev.dtype_code(ts[first])))
+        runs.append((first, count, tile_begin, dev.bits_code(dev.dtype_code(ts[first]))))
         tile_begin += sum(tiles[first:first + count])
     return _remember(_ENC_PLANS, key, {
         'ns': ns, 'offs': offs,
@@ -439,7 +441,7 @@ def _rice_dec_plan(b, hb):
     runs = []
     tile_begin = 0
     for first, count in _runs([torch.empty(0, dtype=dev.CODE_TO_TORCH[c]) for c in codes]):
-        runs.append((first, count, tile_begin, codes[first]))
+        runs.append((first, count, tile_begin, dev.bits_code(codes[first])))
         tile_begin += sum(tiles[first:first + count])
     return {'ns': ns, 'offs': offs, 'shapes': shapes, 'codes': codes, 'dims': tuple(int(d) for d in dims[:nsp]), 'poff': poff,
             'words': words, 'total': total, 'T': sum(tiles), 'runs': runs,
@@ -476,7 +478,7 @@ def _launch_ranges(records, bad):
              arr[q].payload, arr[q].payload_first, arr[q].payload_words) = r
             t0, t1 = _range_tiles(r[3], r[4])
             tiles += t1 - t0 + 1
-        check(lib.kmp_rice_bundle_decode_ranges(records[i][0], arr, k - i, bad.data_ptr(), dev.stream()),
+        check(lib.kmp_rice_bundle_decode_ranges(dev.bits_code(records[i][0]), arr, k - i, bad.data_ptr(), dev.stream()),
               'rice ranges')
         i = k
     return tiles

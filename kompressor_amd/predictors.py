@@ -72,7 +72,12 @@ def resolve_arith(arith, padding, ndim, dtype):
     since round 6) -- and the f32 chain everywhere else (padding 0, where the f32 kernel is the faster
     one; images; 32-bit samples, which bf16x2 cannot split exactly).  A function of the predictor and
     the sample dtype only, so encode, decode, chunked and whole-volume calls, and a file's reader all
-    resolve it the same way."""
+    resolve it the same way.  Signed samples (int8 / int16) resolve to ``'f32'``; an explicit
+    ``'bf16x2'`` with them raises ValueError."""
+    if dtype in dev.UNSIGNED_TWIN:  # signed samples: the f32 chain only (no matrix-core kernels for them)
+        if arith == 'bf16x2':
+            raise ValueError(f"arith='bf16x2' takes uint8 / uint16 samples, not {dtype}: use 'f32' (or 'auto')")
+        return 'f32'
     if arith != 'auto':
         return arith
     return 'bf16x2' if ndim == 3 and padding == 1 and dtype in (torch.uint16, torch.uint8) else 'f32'
@@ -95,7 +100,12 @@ class LinearPredictor:
       uint8 / uint16 samples), ``'f32'`` elsewhere (:func:`resolve_arith`).  Breaking change (round 5,
       uint8 in round 6): the default was ``'f32'``; in-memory encodings made with the old default must
       be decoded with ``arith='f32'`` (files record their arithmetic, and ``container.decompress``
-      takes it from the file for a default-constructed predictor)."""
+      takes it from the file for a default-constructed predictor).
+
+    Signed samples (int8 / int16): the features are ``M(x) = x ^ signbit`` (the samples shifted up by
+    2^(W-1) onto the unsigned range), the chain and its cast run in that domain exactly as for the
+    unsigned type, and the predictions returned are ``M^-1`` of the result, in the signed type.  The
+    weights therefore act on ``M(samples)``; ``arith`` is ``'f32'`` for them."""
 
     def __init__(self, weights, bias, padding=0, ndim=3, arith='auto'):
         if ndim not in (2, 3):
@@ -179,7 +189,11 @@ class LinearPredictor:
         """Least-squares fit on ``highres`` (``[B, spatial..., 1]`` uint8 / uint16, numpy or CUDA
         tensor), or on an iterable of such arrays: moments add, so a sample of tiles, or the chunks
         of a volume too large for one call, fit as the sum of their moments.  The moments are
-        accumulated exactly on the GPU (kmp_fit.hip); the small solve is host float64."""
+        accumulated exactly on the GPU (kmp_fit.hip); the small solve is host float64.
+
+        Signed data (int8 / int16) is fitted in the domain the predictor evaluates in: the moments
+        are those of ``M(x) = x ^ signbit``, features and targets alike, so the weights and the bias
+        apply to ``M(samples)`` and predict ``M(target)``."""
         if isinstance(highres, (np.ndarray, torch.Tensor)):
             highres = (highres,)
         total = None
@@ -210,12 +224,12 @@ def _check_fit_input(highres, padding, ndim):
     """Everything ``linear_moments`` refuses, checked before the device is touched."""
     _check_fit_config(padding, ndim)
     if isinstance(highres, torch.Tensor):
-        ok = highres.dtype in (torch.uint8, torch.uint16)
+        ok = highres.dtype in (torch.uint8, torch.uint16, torch.int8, torch.int16)
     else:
         highres = np.asarray(highres)
-        ok = highres.dtype in (np.dtype(np.uint8), np.dtype(np.uint16))
+        ok = highres.dtype in (np.dtype(np.uint8), np.dtype(np.uint16), np.dtype(np.int8), np.dtype(np.int16))
     if not ok:
-        raise TypeError(f'linear_moments takes uint8 / uint16 samples, not {highres.dtype}')
+        raise TypeError(f'linear_moments takes uint8 / uint16 / int8 / int16 samples, not {highres.dtype}')
     shape = tuple(int(s) for s in highres.shape)
     _require(len(shape) == ndim + 2, f'highres must be [B, {ndim} spatial dims, 1]')
     _require(shape[-1] == 1, 'linear_moments takes single-channel data (C == 1)')
@@ -236,9 +250,12 @@ def linear_moments(highres, padding=0, ndim=3):
     Integers, so exact, order-independent and additive over tiles, chunks and ranks.
 
     ``highres``: ``[B, spatial..., 1]`` uint8 / uint16, numpy or CUDA tensor; volumes take padding
-    0 or 1, images 0, 1 or 2."""
+    0 or 1, images 0, 1 or 2.  int8 / int16 data gives the moments of ``M(x) = x ^ signbit`` (one
+    torch xor ahead of the kernel: fitting is not a hot path)."""
     highres = _check_fit_input(highres, padding, ndim)
     t, _ = dev.to_device(highres)
+    if t.dtype in dev.UNSIGNED_TWIN:
+        t = (t ^ torch.iinfo(t.dtype).min).view(dev.UNSIGNED_TWIN[t.dtype])
     n, k = (2 * padding + 2) ** ndim, NPRED[ndim]
     q = n + k + 1
     code = dev.dtype_code(t)

@@ -28,7 +28,7 @@ def volume_to_tiles(volume, tile, ndim=3):
     n = dev.prod(s // x for s, x in zip(sp, tile))
     out = dev.empty((n, *tile, *ch), t.dtype)
     if t.numel():
-        check(lib.kmp_tiles(ndim, dev.dtype_code(t), 0, t.data_ptr(), _lib.i64x3(sp), dev.prod(ch), _lib.i64x3(tile),
+        check(lib.kmp_tiles(ndim, dev.move_code(t), 0, t.data_ptr(), _lib.i64x3(sp), dev.prod(ch), _lib.i64x3(tile),
                             out.data_ptr(), dev.stream()), 'tiles (split)')
     return dev.from_device(out, kind)
 
@@ -45,6 +45,6 @@ def tiles_to_volume(tiles, shape, ndim=3):
         raise AssertionError(f'{t.shape[0]} tiles of {tile} do not assemble a volume of {shape}')
     out = dev.empty((*shape, *ch), t.dtype)
     if t.numel():
-        check(lib.kmp_tiles(ndim, dev.dtype_code(t), 1, t.data_ptr(), _lib.i64x3(shape), dev.prod(ch),
+        check(lib.kmp_tiles(ndim, dev.move_code(t), 1, t.data_ptr(), _lib.i64x3(shape), dev.prod(ch),
                             _lib.i64x3(tile), out.data_ptr(), dev.stream()), 'tiles (assemble)')
     return dev.from_device(out, kind)

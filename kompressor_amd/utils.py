@@ -6,15 +6,18 @@ carries a ``_kmp_coder`` tag so ``encode`` / ``decode`` can recognise it and run
 one-pass kernel instead of one launch per map.
 """
 
+import torch
+
 from . import _lib
 from ._nd import d_categorical, d_code, validate_padding, yield_chunks  # noqa: F401
 from . import _device as dev
 
 
-def _coder(direction, coder, name, doc):
+def _coder(direction, coder, name, doc, out_dtype=None):
     def fn(pred, x):
         kind = 'torch' if dev.is_torch(x) else 'numpy'
-        return dev.from_device(d_code(direction, coder, pred, x), kind)
+        out = d_code(direction, coder, pred, x)
+        return dev.from_device(out if out_dtype is None else out.view(out_dtype), kind)
     fn.__name__ = fn.__qualname__ = name
     fn.__doc__ = doc
     fn._kmp_coder = (coder, direction)
@@ -39,6 +42,17 @@ encode_values_uint32 = _coder(_lib.ENCODE, _lib.CODER_U32, 'encode_values_uint32
                               'uint32(gt - pred) modulo 2^32 (build extension for bit-cast float32).')
 decode_values_uint32 = _coder(_lib.DECODE, _lib.CODER_U32, 'decode_values_uint32',
                               'uint32(pred + encoded) modulo 2^32 (build extension for bit-cast float32).')
+# Build extension (no reference counterpart): signed samples.  The residual is mod 2^W of the signed
+# difference, stored in the unsigned type of the same width (the same bits as the unsigned coder on
+# the samples' bit patterns); the decoders return the signed type.  DESIGN.md "Signed samples".
+encode_values_int8 = _coder(_lib.ENCODE, _lib.CODER_U8, 'encode_values_int8',
+                            'uint8((gt - pred) mod 2^8) of int8 samples (build extension).')
+decode_values_int8 = _coder(_lib.DECODE, _lib.CODER_U8, 'decode_values_int8',
+                            'int8((pred + encoded) mod 2^8), the signed value (build extension).', torch.int8)
+encode_values_int16 = _coder(_lib.ENCODE, _lib.CODER_U16, 'encode_values_int16',
+                             'uint16((gt - pred) mod 2^16) of int16 samples (build extension).')
+decode_values_int16 = _coder(_lib.DECODE, _lib.CODER_U16, 'decode_values_int16',
+                             'int16((pred + encoded) mod 2^16), the signed value (build extension).', torch.int16)
 
 
 def encode_categorical(pred, gt):

@@ -5,6 +5,8 @@ from ..utils import \
     encode_values_uint8, decode_values_uint8, \
     encode_values_uint16, decode_values_uint16, \
     encode_values_uint32, decode_values_uint32, \
+    encode_values_int8, decode_values_int8, \
+    encode_values_int16, decode_values_int16, \
     encode_categorical, decode_categorical  # noqa: F401
 
 from .utils import \

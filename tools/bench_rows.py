@@ -421,6 +421,55 @@ def main():
                                       'ratio': round(info['ratio'], 3), 'file_bytes': info['bytes'],
                                       'split_ms': {k: round(v * 1e3, 2) for k, v in split.items()}}), flush=True)
 
+    # signed samples (DESIGN.md "Signed samples"): int16 beside uint16 on the same bits (the int16
+    # array is M^-1 of the uint16 one, so both kernels do the same arithmetic), in one process, the
+    # two dtypes' launches alternated per round; the yardstick is the uint16 kernel of this very run
+    # and its own spread over the rounds.  wave3d at C3, wave2d at the C2 shape, generic on odd tiles.
+    if not want or 'signed' in want:
+        rounds, inner = max(5, args.reps), 20
+        for tag, shape, ndim in (('signed_wave3d_c3', (512, 64, 64, 64, 1), 3),
+                                 ('signed_wave2d_c2', (1024, 256, 256, 1), 2),
+                                 ('signed_generic_63', (512, 63, 63, 63, 1), 3)):
+            xu = torch.from_numpy(rand(shape, np.uint16, 3)).cuda()
+            xs = (xu.view(torch.int16) ^ -32768)
+            pred = kom.MeanPredictor(0, ndim)
+            fns, names = {}, {}
+            for key, x in (('uint16', xu), ('int16', xs)):
+                coder = _nd.NATURAL_CODER[x.dtype]
+                lo, maps, dims = _nd._alloc_encoded(x, coder, ndim)
+                rec = torch.empty_like(x)
+                ws = torch.empty(max(1, _nd.workspace_bytes(x, pred, ndim)), dtype=torch.uint8, device='cuda')
+                fe = lambda x=x, coder=coder, lo=lo, maps=maps, ws=ws: _nd.fused_encode_into(  # noqa: E731
+                    x, pred, coder, lo, maps, ndim, workspace=ws)
+                fd = lambda coder=coder, lo=lo, maps=maps, dims=dims, rec=rec, ws=ws: _nd.fused_decode_into(  # noqa: E731
+                    lo, maps, dims, pred, coder, rec, ndim, workspace=ws)
+                fe()
+                names[key] = kom._lib.lib.kmp_last_launch().decode()
+                fd()
+                torch.cuda.synchronize()
+                assert torch.equal(rec, x), (tag, key)
+                fns[key] = {'encode': fe, 'decode': fd, 'maps': maps}
+            assert all(torch.equal(a, b) for a, b in zip(fns['uint16']['maps'], fns['int16']['maps'])), tag
+            times = {(k, d): [] for k in fns for d in ('encode', 'decode')}
+            for _ in range(rounds):
+                for d in ('encode', 'decode'):
+                    for k in ('uint16', 'int16'):
+                        times[(k, d)].append(gpu_time(fns[k][d], inner))
+            raw = xu.numel() * 2
+            for d in ('encode', 'decode'):
+                med = {k: float(np.median(times[(k, d)])) for k in fns}
+                line = {'row': f'{tag}:{d}', 'what': f'{names["int16"]} family, MeanPredictor(0), {shape}; median of '
+                                                   f'{rounds} alternated rounds of {inner} calls',
+                        'algo_bytes': 2 * raw}
+                for k in ('uint16', 'int16'):
+                    t = times[(k, d)]
+                    line[k] = {'us': round(med[k] * 1e6, 2), 'min_us': round(min(t) * 1e6, 2),
+                               'max_us': round(max(t) * 1e6, 2), 'GBps': round(2 * raw / med[k] / 1e9, 1)}
+                line['int16_over_uint16'] = round(med['int16'] / med['uint16'], 4)
+                line['uint16_spread'] = round((max(times[('uint16', d)]) - min(times[('uint16', d)])) / med['uint16'], 4)
+                print(json.dumps(line), flush=True)
+            del xu, xs, fns
+
     # geometry primitives (volume/utils.py) on the C3 tile batch
     if not want or 'primitives' in want:
         hp, _ = _nd.d_pad_highres(vol, 3)                       # [512, 65^3]
