@@ -529,6 +529,7 @@ __device__ __forceinline__ void decode_block8(int param, const int words, const 
   // a group sum (lane m adds 1 to the nibbles j > cum_m >> 3); then one select in that word.
   // No loop and no LDS round trip per word (a walk word by word measured slower)
   uint32_t pos8 = 0;
+  // this encoder's k* has uw <= 7 (uw(k) >= 8: words(k + 1) <= 2k + 3 + ceil(uw / 2) < words(k)); others may not
   const bool short_stream = __all(!(param > 0) || uw <= 8);
   if (short_stream) {
     const uint32_t wm = (param > 0 && j < uw) ? us[j] : 0u;
@@ -722,6 +723,7 @@ __global__ void __launch_bounds__(256) rice_bundle_decode_kernel(RArrs A, int64_
     // a group sum (lane m adds 1 to the nibbles j > cum_m >> 3); then one select in that word.
     // No loop and no LDS round trip per word (a walk word by word measured slower)
     uint32_t pos8 = 0;
+    // this encoder's k* has uw <= 7 (uw(k) >= 8: words(k + 1) <= 2k + 3 + ceil(uw / 2) < words(k)); others may not
     const bool short_stream = __all(!(param > 0) || uw <= 8);
     if (short_stream) {
       const uint32_t wm = (param > 0 && j < uw) ? us[j] : 0u;

@@ -1,9 +1,13 @@
 """Randomised parity sweep of the Rice bundle (spec oracle/rice.py): seeded
 random bundles -- 1-6 arrays of mixed sample dtypes (uint8 / uint16 / int32 / uint32 / float32),
 ragged sizes around the block (64) and tile (16 384 samples) boundaries, and residual
-distributions that reach every path of the kernels: small Laplacian residuals (32-bit unary masks,
-short streams), wide spreads (large k), single spikes and lopsided lanes (a lane's 8 codes past 32
-and 64 bits, unary streams past 8 words: the word-walk fallbacks), all-zero blocks and runs.  Each
+distributions of several regimes: small Laplacian residuals (32-bit unary masks), wide spreads
+(large k), single spikes and lopsided lanes (a lane's 8 codes past 32 and 64 bits: the 64-bit window
+and the per-lane word walk of the decoders), all-zero blocks and runs.  What this data cannot reach
+is the decoders' ``!short_stream`` branch, the word walk to a lane's START for unary streams past 8
+words: the encoder's k* keeps every stream within 7 words (tests/rice_spec.py has the argument, a
+census of which paths data reaches, and bundles with a forced k that do take that branch:
+test_gpu_rice_paths.py).  Each
 bundle is packed by the HIP kernels (one single-pass launch per run of same-dtype arrays), compared
 byte for byte with the numpy specification, and unpacked losslessly.  120 cases by default
 (KMP_FUZZ_RICE_CASES, first seed KMP_FUZZ_SEED0)."""

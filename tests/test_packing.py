@@ -123,8 +123,11 @@ def test_rice_matches_spec(kom, dtype, shape, spread):
 def test_rice_long_unary_runs(kom, dtype):
     """Blocks whose unary part is lopsided: the 8 samples of one lane (8 consecutive samples) are
     large and the rest of the block small, so that lane's 8 codes span more than 64 stream bits and
-    the unpack kernel leaves its 64-bit window path for the word-by-word walk; every lane position,
-    several magnitudes, and single spikes.  Byte-exact to the spec, lossless."""
+    the unpack kernel leaves its 64-bit window path for the per-lane word-by-word walk over those
+    codes; every lane position, several magnitudes, and single spikes.  Byte-exact to the spec,
+    lossless.  (The other walk, to a lane's start when a stream is longer than 8 words --
+    ``!short_stream`` -- is not reached here or by any encoded data: k* keeps streams within 7 words;
+    test_gpu_rice_paths.py reaches it with a forced k.)"""
     rng = np.random.default_rng(11)
     W = np.dtype(dtype).itemsize * 8
     top = (1 << min(W, 16)) - 1
