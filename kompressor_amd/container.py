@@ -13,6 +13,8 @@ sample dtype (float32 volumes travel bit-cast to uint32) and a CRC-32 of the pay
     highres = decompress(path)                    # read + unpack + decode on the GPU
     save(path, lowres, encoded, predictor=...)    # an encode() result you already have
     lowres, encoded, meta = load(path)
+    box = read_region(path, planes=(z0, z1), rows=(y0, y1), cols=(x0, x1), level=k)   # only the tiles the box needs
+    shapes = level_shapes(path)                   # header + metadata only
 
 File layout (little-endian): ``b'KMPF' u16 version u16 0 u64 meta_len``, the metadata as UTF-8
 JSON padded to 8 bytes, then the ``pack_encoded`` bundle (``meta['bundle_bytes']`` bytes).  A file
@@ -479,10 +481,15 @@ def _coder_fn(coder, ndim):
 # map planes only).  ``plan_region`` composes the two down the pyramid; ``read_region`` preads
 # the table, side-information and payload windows of the touched tiles, decodes them with
 # kmp_rice_bundle_decode_ranges into local arrays and runs the fused decode's z-region level by
-# level, coarsest first.
+# level, coarsest first.  The same recurrence runs on every spatial axis (rows=, cols=: the local
+# arrays are cropped along z and y, the box is the fused decode's region) and may stop at any
+# pyramid level (level=): DESIGN.md §15.
 # ---------------------------------------------------------------------------------------------
 
 _TILE = 16384  # samples per tile of a v2 Rice bundle (256 blocks of 64)
+# a level whose plane of cells holds at most this many samples is not cropped along rows: a row run
+# touches the same tile as its whole plane, so consecutive planes would decode one tile repeatedly
+_ROW_CROP_PLANE = _TILE
 _CRC_TABLE_WHOLE = 256 << 10  # a per-tile CRC table up to this size is read whole when several ranges need entries
 
 
@@ -591,64 +598,139 @@ def _tiles(n):
     return -(-(-(-n // 64)) // 256) if n > 0 else 0
 
 
-def plan_region(meta, planes=None, batch=None):
-    """The arrays a selection needs, as a pure function of the file's metadata.  ``planes = (z0, z1)``
-    selects highres planes along the first spatial axis (volumes only), ``batch = (b0, b1)`` items of
-    the leading axis; both are clamped to the array, an empty or reversed range raises ValueError.
+def _check_level(level, nlev):
+    if isinstance(level, bool) or not isinstance(level, (int, np.integer)) or not 0 <= level <= nlev:
+        raise ValueError(f'level={level!r}: a file of {nlev} coded levels has levels 0 .. {nlev}')
+    return int(level)
 
-    From the finest level down, highres planes ``[a, b)`` of a level are its output planes
-    ``(a // 2, (b + 1) // 2)``, which need the lowres planes ``slabs.decode_halo`` of them -- the next
-    level's highres planes -- and each map's planes ``[z0, min(z1, the map's z extent))``.  Returns
-    ``{'batch', 'planes', 'levels': [{'highres', 'out', 'lowres', 'maps', 'at_top', 'dims'}] finest
-    first, 'lowres': the coarsest lowres planes, 'arrays': one entry per bundle array in bundle order
-    (the coarsest lowres, then every level's maps, finest first) with its full ``shape``, the selected
-    planes ``sel``, the ``local_shape`` it is decoded into, the plane ``local_at`` the selection starts
-    at there and ``ranges`` [(first sample, end sample, destination sample)], 'tiles_decoded',
-    'tiles_total'}``."""
+
+def _refuse_image_planes(ndim, planes):
+    if planes is not None and ndim != 3:
+        raise ValueError('planes selects along the first spatial axis of a volume; an image file takes rows, cols '
+                         'and batch')
+
+
+def _selection(ndim, top, planes, rows, cols):
+    """The clamped span of every spatial axis of the level-``k`` array of shape ``top``."""
+    _refuse_image_planes(ndim, planes)
+    named = (('planes', planes), ('rows', rows), ('cols', cols))[3 - ndim:]
+    return [_clamp_range(r, top[1 + a], name) for a, (name, r) in enumerate(named)]
+
+
+def plan_region(meta, planes=None, batch=None, rows=None, cols=None, level=0):
+    """The arrays a selection needs, as a pure function of the file's metadata.  ``level = k`` selects
+    pyramid level ``k`` (0: the array ``decompress`` returns; ``L``, the number of coded levels: the
+    stored coarsest lowres; level ``k`` is level 0 strided by ``2**k``) and every range is in that
+    level's coordinates: ``planes``, ``rows`` and ``cols`` select along z, y and x of a volume,
+    ``rows`` and ``cols`` along y and x of an image (``planes`` raises ValueError there),
+    ``batch = (b0, b1)`` items of the leading axis.  Ranges are clamped to the array, an empty or
+    reversed one raises ValueError, and so does a ``level`` outside ``[0, L]``.
+
+    From level ``k`` down, on every spatial axis, highres span ``[s, e)`` of a level is its output
+    span ``(s // 2, (e + 1) // 2)``, which needs the lowres span ``slabs.decode_halo`` of it -- the
+    next level's highres span -- and each map's span ``[o0, min(o1, the map's extent))``.  The local
+    arrays a level is decoded from are cropped to these spans along the first spatial axis and, for
+    volumes, the second; never along the last one (rows are the contiguous unit of the format), whose
+    span restricts the codec's region and the final slice only.  From the finest level whose plane of
+    cells fits ``_ROW_CROP_PLANE`` samples on, the second axis is not cropped either (a row run would
+    touch the plane's one tile anyway).  The even-size ``dims`` apply to a level's local arrays on
+    the axes where its local lowres reaches the last node (``at_top``).
+
+    Returns ``{'batch', 'planes', 'rows', 'cols', 'box': the clamped span per spatial axis, 'level',
+    'levels': [{'index', 'highres', 'out', 'lowres', 'maps', 'at_top', 'dims' (the first spatial axis,
+    as before), 'axes': per spatial axis {'highres', 'out', 'lowres', 'local': the lowres span the
+    local arrays hold, 'at_top', 'crop': the span of the level's local output the level above (or the
+    selection) keeps}, 'rows', 'cols': the 'axes' entry of that axis, 'at_top_axes'}] from level ``k``
+    to the coarsest, 'lowres': the coarsest lowres' span on the first axis, 'lowres_axes': its local
+    span per axis, 'arrays': one entry per bundle array in bundle order (the coarsest lowres, then
+    every level's maps, finest first) with its full ``shape``, the selected spans ``sel`` (first axis)
+    and ``sel_rows``, the ``local_shape`` it is decoded into (None for the maps of levels finer than
+    ``k``, which have no ranges), the offsets ``local_at`` and ``local_row_at`` the selection starts at
+    there and ``ranges`` [(first sample, end sample, destination sample)] -- one per array, one per
+    batch item when only the first axis is restricted, one per batch item and plane (a row run) where
+    rows are cropped --, 'tiles_decoded': tiles the launches decode, counted per range,
+    'tiles_total': tiles in the file}``."""
     ndim, p = int(meta['ndim']), int(meta['padding'])
     shapes = _meta_shapes(meta)
-    full = shapes[0][0]
-    if planes is not None and ndim != 3:
-        raise ValueError('planes selects along the first spatial axis of a volume; an image file takes batch only')
-    b0, b1 = _clamp_range(batch, full[0], 'batch')
-    a, b = _clamp_range(planes, full[1], 'planes')
+    nlev = len(shapes)
+    nmaps = _nd.NMAPS[ndim]
+    _refuse_image_planes(ndim, planes)
+    level = _check_level(level, nlev)
+    top = shapes[level][0] if level < nlev else shapes[-1][1]
+    b0, b1 = _clamp_range(batch, top[0], 'batch')
+    box = _selection(ndim, top, planes, rows, cols)
     bsel = b1 - b0
+    ncrop = ndim - 1  # the leading spatial axes local arrays are cropped along
 
-    def entry(shape, sel, local_z, local_at):
-        per = dev.prod(shape[2:])
-        z = shape[1]
-        s0, s1 = sel
-        local_shape = (bsel, local_z, *shape[2:])
-        if s1 <= s0:
-            ranges = []
-        elif (s0, s1) == (0, z) and local_z == z:
-            ranges = [(b0 * z * per, b1 * z * per, 0)]
-        else:
-            ranges = [((bi * z + s0) * per, (bi * z + s1) * per, ((bi - b0) * local_z + local_at) * per)
-                      for bi in range(b0, b1)]
-        return {'shape': tuple(shape), 'sel': (s0, max(s0, s1)), 'local_shape': local_shape, 'local_at': local_at,
-                'ranges': ranges}
+    def entry(shape, sels, local_ext, local_at):
+        """``sels``, ``local_ext``, ``local_at``: per cropped axis, the selected span of the array, the
+        local array's extent and where the selection starts in it."""
+        (s0, s1), z, local_z = sels[0], shape[1], local_ext[0]
+        empty = any(e <= s for s, e in sels)
+        out = {'shape': tuple(shape), 'sel': (s0, max(s0, s1)), 'local_shape': (bsel, *local_ext, *shape[1 + ncrop:]),
+               'local_at': local_at[0], 'sel_rows': (sels[-1][0], max(sels[-1])), 'local_row_at': local_at[-1]}
+        if empty:
+            out['ranges'] = []
+        elif ncrop == 1 or (sels[1] == (0, shape[2]) and local_ext[1] == shape[2]):
+            per = dev.prod(shape[2:])
+            if (s0, s1) == (0, z) and local_z == z:
+                out['ranges'] = [(b0 * z * per, b1 * z * per, 0)]
+            else:
+                out['ranges'] = [((bi * z + s0) * per, (bi * z + s1) * per, ((bi - b0) * local_z + local_at[0]) * per)
+                                 for bi in range(b0, b1)]
+        else:  # one row run per batch item and selected plane, compact in the local array
+            (r0, r1), y, local_y, per = sels[1], shape[2], local_ext[1], dev.prod(shape[3:])
+            out['ranges'] = [(((bi * z + zi) * y + r0) * per, ((bi * z + zi) * y + r1) * per,
+                              (((bi - b0) * local_z + local_at[0] + zi - s0) * local_y + local_at[1]) * per)
+                             for bi in range(b0, b1) for zi in range(s0, s1)]
+        return out
 
+    def small_plane(lo_shape):  # the row-crop threshold: a plane of cells within one tile
+        return ndim == 3 and dev.prod(lo_shape[2:]) <= _ROW_CROP_PLANE
+
+    span, target, widened = list(box), list(box), False
     levels, map_entries = [], []
-    for h, lo_shape, map_shapes, dims in shapes:
-        E = lo_shape[1]
-        z0, z1 = a // 2, (b + 1) // 2
-        lo, hi = max(0, z0 - 1 - p), min(E, z1 + p + 1)  # slabs.decode_halo
-        at_top = hi == E
-        El = hi - lo
-        Ll = El + (dims[0] if at_top else 0)
+    for j in range(level, nlev):
+        h, lo_shape, map_shapes, dims = shapes[j]
+        if widened or small_plane(lo_shape):
+            widened = True
+            span[1] = (0, h[2])
+        axes = []
+        for a in range(ndim):
+            s, e = span[a]
+            E = lo_shape[1 + a]
+            o0, o1 = s // 2, (e + 1) // 2
+            need = (max(0, o0 - 1 - p), min(E, o1 + p + 1))  # slabs.decode_halo
+            local = need if a < ncrop else (0, E)
+            axes.append({'highres': (s, e), 'out': (o0, o1), 'lowres': need, 'local': local, 'at_top': local[1] == E,
+                         'crop': (target[a][0] - 2 * local[0], target[a][1] - 2 * local[0])})
+        El = [A['local'][1] - A['local'][0] for A in axes]
+        Ll = [el + (dims[a] if axes[a]['at_top'] else 0) for a, el in enumerate(El)]
         msel = []
         for par, ms in zip(_nd.PARITY[ndim], map_shapes):
-            sel = (z0, min(z1, ms[1]))
-            msel.append((sel[0], max(sel)))
-            map_entries.append(entry(ms, sel, Ll - 1 if par[0] else El, z0 - lo))
-        levels.append({'highres': (a, b), 'out': (z0, z1), 'lowres': (lo, hi), 'maps': msel, 'at_top': at_top,
-                       'dims': tuple(dims)})
-        a, b = lo, hi
-    arrays = [entry(shapes[-1][1], (a, b), b - a, 0)] + map_entries
+            sels = [(A['out'][0], min(A['out'][1], ms[1 + a])) for a, A in enumerate(axes[:ncrop])]
+            msel.append((sels[0][0], max(sels[0])))
+            map_entries.append(entry(ms, sels, [Ll[a] - 1 if par[a] else El[a] for a in range(ncrop)],
+                                     [A['out'][0] - A['local'][0] for A in axes[:ncrop]]))
+        levels.append({'index': j, 'highres': axes[0]['highres'], 'out': axes[0]['out'], 'lowres': axes[0]['lowres'],
+                       'maps': msel, 'at_top': axes[0]['at_top'], 'dims': tuple(dims), 'axes': axes,
+                       'rows': axes[ndim - 2], 'cols': axes[ndim - 1],
+                       'at_top_axes': tuple(A['at_top'] for A in axes)})
+        span = [A['lowres'] for A in axes]
+        target = [A['local'] for A in axes]
+    lo_shape = shapes[-1][1]
+    if level == nlev and small_plane(lo_shape):
+        target[1] = (0, lo_shape[2])
+    lowres_axes = [target[a] if a < ncrop else (0, lo_shape[1 + a]) for a in range(ndim)]
+    skipped = [{'shape': tuple(ms), 'sel': (0, 0), 'local_shape': None, 'local_at': 0, 'sel_rows': (0, 0),
+                'local_row_at': 0, 'ranges': []} for _, _, map_shapes, _ in shapes[:level] for ms in map_shapes]
+    arrays = [entry(lo_shape, lowres_axes[:ncrop], [e - s for s, e in lowres_axes[:ncrop]], [0] * ncrop)] + \
+        skipped + map_entries
+    assert len(arrays) == 1 + nmaps * nlev
     for i, e in enumerate(arrays):
         e['index'] = i
-    return {'batch': (b0, b1), 'planes': levels[0]['highres'], 'levels': levels, 'lowres': (a, b), 'arrays': arrays,
+    return {'batch': (b0, b1), 'planes': box[0], 'rows': box[ndim - 2], 'cols': box[ndim - 1], 'box': tuple(box),
+            'level': level, 'levels': levels, 'lowres': lowres_axes[0], 'lowres_axes': lowres_axes, 'arrays': arrays,
             'tiles_decoded': sum((e - 1) // _TILE - f // _TILE + 1 for ar in arrays for f, e, _ in ar['ranges']),
             'tiles_total': sum(_tiles(dev.prod(ar['shape'])) for ar in arrays)}
 
@@ -666,11 +748,16 @@ def _region_windows(fd, path, base, nbytes, rplan, plan, crc_table=None):
     range the buffer offset of its tiles' CRC entries)``.  ``crc_table = (offset of the file's
     per-tile CRC table from the bundle's start, T)`` (validated by the caller) reads the touched
     tiles' u32 entries into the same buffer -- each range's are contiguous -- or the whole table at
-    once when that is fewer reads and it is small; without it the last result is empty."""
+    once when that is fewer reads and it is small; without it the last result is empty.
+
+    The ranges of one array and batch item (the row runs of a box selection) share ONE read of the
+    tile table and ONE of each side-information array, from their first through their last touched
+    tile (8 bytes per tile, 2 per block: the span costs less than a read per run); each range's
+    records point into the span.  The payload is one read per range."""
     poff, words = rplan['poff'], rplan['words']
     if rplan['total'] > nbytes:
         raise ValueError(f'{path}: the bundle records {rplan["total"]} bytes, the file holds {nbytes}')
-    jobs, used, payload_bytes = [], 0, 0
+    jobs, groups, used, payload_bytes = [], [], 0, 0
     for ar in plan['arrays']:
         i = ar['index']
         n, code = rplan['ns'][i], rplan['codes'][i]
@@ -678,68 +765,99 @@ def _region_windows(fd, path, base, nbytes, rplan, plan, crc_table=None):
         side, toff = rplan['offs'][i]
         nb, nt = -(-n // 64), _tiles(n)
         w_first, w_end = rplan['spans'][i]
+        per_item = max(dev.prod(ar['shape'][1:]), 1)
+        by_item = {}  # the ranges of one batch item (ascending) share one table and one side-information span
         for rng in ar['ranges']:
-            t0, t1 = rng[0] // _TILE, (rng[1] - 1) // _TILE
-            cnt = t1 - t0 + 1
-            have = cnt + 1 if t1 + 1 < nt else cnt  # the table has no entry after the last tile
+            by_item.setdefault(rng[0] // per_item, []).append(rng)
+        for rngs in by_item.values():
+            g0, g1 = rngs[0][0] // _TILE, max((r[1] - 1) // _TILE for r in rngs)
+            cnt = g1 - g0 + 1
+            have = cnt + 1 if g1 + 1 < nt else cnt  # the table has no entry after the last tile
             tab = np.empty((cnt + 1,), np.uint64)
-            _pread_exact(fd, tab[:have].view(np.uint8), base + toff + 8 * t0, path)
+            _pread_exact(fd, tab[:have].view(np.uint8), base + toff + 8 * g0, path)
             if have == cnt:
                 tab[cnt] = w_end
-            tl = [int(v) for v in tab]
-            if (t0 == 0 and tl[0] != w_first) or tl[0] < w_first or tl[-1] > w_end or w_end > words or \
-                    any(y < x or y - x > 256 * (2 * W + 2) for x, y in zip(tl, tl[1:])):
-                raise ValueError(f'{path}: tile table of array {i} is inconsistent (corrupt file)')
-            pw = tl[-1] - tl[0]
-            if poff + 4 * tl[-1] > nbytes:
-                raise ValueError(f'{path}: payload window of array {i} lies outside the file')
-            nside = min(nb, 256 * (t1 + 1)) - 256 * t0
+            nside = min(nb, 256 * (g1 + 1)) - 256 * g0
             o_t = used
             o_p = o_t + 8 * (cnt + 1)
             o_b = o_p + nside
-            o_w = (o_b + nside + 7) & ~7
-            used = (o_w + 4 * pw + 7) & ~7
-            jobs.append((ar, rng, tab, (o_t, o_p, o_b, o_w, tl[0], pw), (side + 256 * t0, nside,
-                                                                           side + ((nb + 7) & ~7) + 256 * t0)))
-            payload_bytes += 4 * pw
+            used = (o_b + nside + 7) & ~7
+            groups.append((tab, o_t, o_p, o_b, nside, side + 256 * g0, side + ((nb + 7) & ~7) + 256 * g0,
+                           len(jobs), len(rngs), g0, cnt))
+            for rng in rngs:  # the entries of the tiles a range touches: checked before they size anything
+                t0, t1 = rng[0] // _TILE, (rng[1] - 1) // _TILE
+                tl = [int(v) for v in tab[t0 - g0:t1 - g0 + 2]]
+                if (t0 == 0 and tl[0] != w_first) or tl[0] < w_first or tl[-1] > w_end or w_end > words or \
+                        any(y < x or y - x > 256 * (2 * W + 2) for x, y in zip(tl, tl[1:])):
+                    raise ValueError(f'{path}: tile table of array {i} is inconsistent (corrupt file)')
+                pw = tl[-1] - tl[0]
+                if poff + 4 * tl[-1] > nbytes:
+                    raise ValueError(f'{path}: payload window of array {i} lies outside the file')
+                o_w = used
+                used = (o_w + 4 * pw + 7) & ~7
+                jobs.append((ar, rng, (o_t + 8 * (t0 - g0), o_p + 256 * (t0 - g0), o_b + 256 * (t0 - g0), o_w, tl[0],
+                                       pw)))
+                payload_bytes += 4 * pw
     crc_reads, crc_offs = [], []  # (buffer offset, bytes, file offset from the bundle's start)
     if crc_table is not None and jobs:
         c_off, T = crc_table
         begins = _tile_begins([_tiles(n) for n in rplan['ns']])
-        spans = [(begins[ar['index']] + rng[0] // _TILE, (rng[1] - 1) // _TILE - rng[0] // _TILE + 1)
-                 for ar, rng, *_ in jobs]  # (first global tile, tiles) per range
         if len(jobs) > 1 and 4 * T <= _CRC_TABLE_WHOLE:
             crc_reads.append((used, 4 * T, c_off))
-            crc_offs = [used + 4 * g for g, _ in spans]
+            crc_offs = [used + 4 * (begins[ar['index']] + rng[0] // _TILE) for ar, rng, _ in jobs]
             used = (used + 4 * T + 7) & ~7
-        else:
-            for g, cnt in spans:
-                crc_reads.append((used, 4 * cnt, c_off + 4 * g))
-                crc_offs.append(used)
+        else:  # one read per group: the entries of its first through last touched tile
+            for *_, j0, nj, g0, cnt in groups:
+                for ar, rng, _ in jobs[j0:j0 + nj]:
+                    crc_offs.append(used + 4 * (rng[0] // _TILE - g0))
+                crc_reads.append((used, 4 * cnt, c_off + 4 * (begins[jobs[j0][0]['index']] + g0)))
                 used = (used + 4 * cnt + 7) & ~7
     buf = dev.pinned_staging(max(used, 8), 'region')
     hv = buf.numpy()
-    out = []
-    for ar, rng, tab, offs, (f_p, nside, f_b) in jobs:
-        o_t, o_p, o_b, o_w, w0, pw = offs
+    for tab, o_t, o_p, o_b, nside, f_p, f_b, *_ in groups:
         hv[o_t:o_t + tab.nbytes] = tab.view(np.uint8)
         _pread_exact(fd, hv[o_p:o_p + nside], base + f_p, path)
         _pread_exact(fd, hv[o_b:o_b + nside], base + f_b, path)
+    for ar, rng, (_, _, _, o_w, w0, pw) in jobs:
         if pw:
             _pread_exact(fd, hv[o_w:o_w + 4 * pw], base + poff + 4 * w0, path)
-        out.append((ar, rng, offs))
     for o, nb_, f_o in crc_reads:
         _pread_exact(fd, hv[o:o + nb_], base + f_o, path)
-    return buf, used, out, payload_bytes, crc_offs
+    return buf, used, jobs, payload_bytes, crc_offs
 
 
-def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, verify=False, tile_crc=True):
-    """``decompress(path)[b0:b1, z0:z1]`` -- bit for bit, shape ``[b1 - b0, z1 - z0, H, W, C...]`` in
-    the file's sample dtype -- reading, uploading and decoding only what the selection needs.
+def level_shapes(path):
+    """The shape of every pyramid level of a file, from its header and metadata alone (no payload
+    read, no GPU): ``[level 0 (the array decompress returns), level 1, ..., level L]`` for a file of
+    ``L`` coded levels -- level ``L`` is the stored coarsest lowres, level ``k`` is level 0 strided by
+    ``2**k`` along every spatial axis, and each is what ``read_region(path, level=k)`` returns."""
+    with open(path, 'rb') as f:
+        _, meta, _, _ = _read_head(f, path)
+    try:
+        shapes = _meta_shapes(meta)
+    except (KeyError, TypeError, IndexError) as e:
+        raise ValueError(f'{path}: corrupt metadata ({e!r})') from None
+    return [tuple(h) for h, _, _, _ in shapes] + [tuple(shapes[-1][1])]
+
+
+def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, verify=False, tile_crc=True,
+                rows=None, cols=None, level=0):
+    """``decompress(path)[b0:b1, z0:z1, y0:y1, x0:x1]`` -- bit for bit, contiguous, in the file's
+    sample dtype -- reading, uploading and decoding only what the selection needs.
     ``batch=(b0, b1)`` selects items of the leading axis (any file: "tile 37" of a tiled file is
-    ``batch=(37, 38)``); ``planes=(z0, z1)`` highres planes along the first spatial axis of a volume
-    file (an image file raises ValueError).  Ranges are clamped; an empty one raises ValueError.
-    ``predictor`` as for :func:`decompress`.
+    ``batch=(37, 38)``); ``planes=(z0, z1)``, ``rows=(y0, y1)`` and ``cols=(x0, x1)`` select along z,
+    y and x of a volume file, ``rows`` and ``cols`` along y and x of an image file (``planes`` raises
+    ValueError there).  ``level=k`` reads pyramid level ``k`` instead (:func:`level_shapes`): the
+    result is ``decompress(path)[:, ::2**k, ::2**k, ::2**k][b0:b1, z0:z1, y0:y1, x0:x1]`` and every
+    range is in level-``k`` coordinates; the arrays of finer levels are neither read nor decoded, and
+    ``level=L`` (the stored coarsest lowres) runs no codec kernel.  Ranges are clamped; an empty one
+    raises ValueError, and so does a ``level`` outside ``[0, L]``.  ``predictor`` as for
+    :func:`decompress`.
+
+    What a range saves: planes and (for a volume whose planes exceed one tile, ``plan_region``) rows
+    crop the arrays read and decoded; a column range does not -- rows are the format's contiguous
+    unit, every touched row is read and Rice-decoded whole -- but restricts the codec's region and
+    the samples returned.
 
     Integrity: a partial read cannot check the bundle's CRC-32 and does not.  Every table entry read
     is validated on the host, and the decode checks the side information of every tile it touches
@@ -753,8 +871,8 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
     ``verify=True`` first reads and CRC-checks the whole bundle, then decodes only the region.
 
     Files without a v2 Rice bundle ('planes' files, version-1 files) are read by a full
-    :func:`decompress` plus a slice (``last_timing['partial']`` is False).  Host and device memory
-    are proportional to the selection (plus its halo planes at every level)."""
+    :func:`decompress` plus a stride and a slice (``last_timing['partial']`` is False).  Host and
+    device memory are proportional to the selection (plus its halo at every level, in full rows)."""
     t0 = time.perf_counter()
     if verify:
         vmeta, vblob, vcrc, _ = _read(path)
@@ -767,19 +885,24 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
         hb = os.pread(fd, min(packing._RHEAD.size, nbytes), base)
         partial = version >= 2 and meta.get('method') == 'rice' and hb[:4] == packing.BUNDLE_MAGIC and \
             len(hb) == packing._RHEAD.size and struct.unpack('<H', hb[4:6])[0] == packing.RICE_VERSION
-        if not partial:  # no tile table to address: the whole file, then the slice
-            if planes is not None and meta.get('ndim') != 3:
-                raise ValueError('planes selects along the first spatial axis of a volume; an image file takes '
-                                 'batch only')
+        if not partial:  # no tile table to address: the whole file, then the stride and the slice
+            try:
+                ndim = int(meta['ndim'])
+                level = _check_level(level, len(_meta_shapes(meta)))
+            except (KeyError, TypeError, IndexError) as e:
+                raise ValueError(f'{path}: corrupt metadata ({e!r})') from None
+            _refuse_image_planes(ndim, planes)  # before the decode, not after
             out = decompress(path, predictor, as_numpy)
+            if level:
+                out = out[(slice(None), *[slice(None, None, 2 ** level)] * ndim)]
             b0, b1 = _clamp_range(batch, out.shape[0], 'batch')
-            z0, z1 = _clamp_range(planes, out.shape[1], 'planes')
-            out = out[b0:b1, z0:z1] if planes is not None else out[b0:b1]
+            box = _selection(ndim, out.shape, planes, rows, cols)
+            out = out[(slice(b0, b1), *[slice(s, e) for s, e in box])]
             last_timing.update(partial=False, tiles_decoded=0, tiles_total=0, payload_bytes_read=int(nbytes),
-                               bundle_bytes=int(nbytes), total=time.perf_counter() - t0, tile_crc=False)
+                               bundle_bytes=int(nbytes), total=time.perf_counter() - t0, tile_crc=False, level=level)
             return np.ascontiguousarray(out) if as_numpy else out.contiguous()
         try:
-            plan = plan_region(meta, planes, batch)
+            plan = plan_region(meta, planes, batch, rows, cols, level)
         except (KeyError, TypeError, IndexError) as e:
             raise ValueError(f'{path}: corrupt metadata ({e!r})') from None
         # the file's per-tile CRC table, checked against the file's size and the metadata's shapes
@@ -803,10 +926,12 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
         buf, used, jobs, payload_bytes, crc_offs = _region_windows(fd, path, base, nbytes, rplan, plan, trailer)
     t1 = time.perf_counter()
     # ---- one upload of all windows, one ranged decode per run of 32 same-dtype records into the
-    # local arrays (planes outside the selection stay unwritten: the z-region never reads them) ----
+    # local arrays (samples outside the selection stay unwritten: the codec's region never reads
+    # them; the maps of levels finer than the one asked for have no local array) ----
     win = dev.empty((max(used, 8),), torch.uint8)
     win[:used].copy_(buf[:used], non_blocking=True)
-    local = [dev.empty(ar['local_shape'], dev.CODE_TO_TORCH[rplan['codes'][ar['index']]]) for ar in arrays]
+    local = [dev.empty(ar['local_shape'], dev.CODE_TO_TORCH[rplan['codes'][ar['index']]])
+             if ar['local_shape'] is not None else None for ar in arrays]
     wp = win.data_ptr()
     records = []
     for ar, (first, end, dst), (o_t, o_p, o_b, o_w, w0, pw) in jobs:
@@ -821,34 +946,38 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
             [(rplan['ns'][ar['index']], first // _TILE, (end - 1) // _TILE, wp + o_p, wp + o_b, wp + o_t,
               wp + o_t + 8 * ((end - 1) // _TILE - first // _TILE + 1), wp + o_w, w0, pw, None, wp + o_e)
              for (ar, (first, end, _), (o_t, o_p, o_b, o_w, w0, pw)), o_e in zip(jobs, crc_offs)], bad[1:])
-    # ---- the pyramid, coarsest level first, each level's z-region on its local arrays ----
+    # ---- the pyramid, coarsest level first down to the level asked for, each level's region (the z
+    # slab alone where the cross-section is whole, else the box) on its local arrays ----
     ndim, padding = meta['ndim'], meta['padding']
     nmaps = _nd.NMAPS[ndim]
     coder = _nd.NATURAL_CODER[dtype]
     dec_fn = _coder_fn(coder, ndim)
     x = local[0]
-    for lvl in reversed(range(len(plan['levels']))):
-        L = plan['levels'][lvl]
+    for L in reversed(plan['levels']):
+        lvl, ax = L['index'], L['axes']
         maps = local[1 + nmaps * lvl:1 + nmaps * (lvl + 1)]
-        ldims = ((L['dims'][0] if L['at_top'] else 0), *L['dims'][1:])
+        ldims = tuple(d if A['at_top'] else 0 for d, A in zip(L['dims'], ax))
         E = _nd._sp(x.shape, ndim)
-        r0, r1 = L['out'][0] - L['lowres'][0], L['out'][1] - L['lowres'][0]
-        whole = r0 == 0 and r1 == E[0]
+        region = [(A['out'][0] - A['local'][0], A['out'][1] - A['local'][0]) for A in ax]
+        whole = all(r == (0, e) for r, e in zip(region, E))
         if _nd.fused_plan(pred, dec_fn, padding, x.dtype, ndim, 1) is not None:
             out = dev.empty((x.shape[0], *[2 * e - 1 + d for e, d in zip(E, ldims)], *x.shape[1 + ndim:]), x.dtype)
-            region = None if whole else [(r0, r1), *[(0, e) for e in E[1:]]]
-            _nd.fused_decode_into(x, maps, ldims, pred, coder, out, ndim, region=region)
+            _nd.fused_decode_into(x, maps, ldims, pred, coder, out, ndim, region=None if whole else region)
         else:
             if not whole:  # an opaque predictions_fn decodes the whole local array: no stray values in it
                 for m, ar in zip(maps, arrays[1 + nmaps * lvl:1 + nmaps * (lvl + 1)]):
-                    keep = m[:, ar['local_at']:ar['local_at'] + ar['sel'][1] - ar['sel'][0]].clone()
+                    sl = [slice(None), slice(ar['local_at'], ar['local_at'] + ar['sel'][1] - ar['sel'][0])]
+                    if ndim == 3:
+                        sl.append(slice(ar['local_row_at'], ar['local_row_at'] + ar['sel_rows'][1] - ar['sel_rows'][0]))
+                    keep = m[tuple(sl)].clone()
                     m.view(torch.uint8).zero_()
-                    m[:, ar['local_at']:ar['local_at'] + keep.shape[1]] = keep
+                    m[tuple(sl)] = keep
             out = _nd.decode(pred, dec_fn, x, (maps, ldims), padding, ndim)
-        a, b = L['highres']
-        x = out[:, a - 2 * L['lowres'][0]:b - 2 * L['lowres'][0]]
-        if lvl:
+        x = out[(slice(None), *[slice(*A['crop']) for A in ax])]
+        if lvl > plan['level']:
             x = x.contiguous()
+    if not plan['levels']:  # the stored coarsest lowres itself
+        x = x[(slice(None), *[slice(s - lo, e - lo) for (s, e), (lo, _) in zip(plan['box'], plan['lowres_axes'])])]
     if meta.get('sample_dtype') == 'float32':
         x = x.contiguous().view(torch.float32)
     nbad, ncrc = bad.tolist()  # the synchronisation
@@ -857,10 +986,11 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
     if ncrc:
         raise ValueError(f'{path}: tile CRC mismatch in {ncrc} of the {tiles} tiles read (corrupt file)')
     t2 = time.perf_counter()
-    out = dev.to_host(x) if as_numpy else x.contiguous()
+    out = np.ascontiguousarray(dev.to_host(x)) if as_numpy else x.contiguous()
     t3 = time.perf_counter()
     last_timing.clear()
     last_timing.update(read=t1 - t0, device=t2 - t1, d2h=t3 - t2, total=t3 - t0, partial=True,
                        tiles_decoded=int(tiles), tiles_total=int(plan['tiles_total']),
-                       payload_bytes_read=int(payload_bytes), bundle_bytes=int(nbytes), tile_crc=bool(crc_offs))
+                       payload_bytes_read=int(payload_bytes), bundle_bytes=int(nbytes), tile_crc=bool(crc_offs),
+                       level=plan['level'])
     return out
