@@ -45,7 +45,19 @@ typedef enum {
 typedef enum { KMP_U8 = 0, KMP_U16 = 1, KMP_I32 = 2, KMP_F32 = 3, KMP_U32 = 4, KMP_I8 = 5, KMP_I16 = 6 } kmp_dtype;
 
 /* Residual coders, utils.py:28-55 (+ the build's mod-2^32 coder for bit-cast float32). */
-typedef enum { KMP_CODER_RAW = 0, KMP_CODER_U8 = 1, KMP_CODER_U16 = 2, KMP_CODER_U32 = 3 } kmp_coder;
+typedef enum {
+  KMP_CODER_RAW = 0, KMP_CODER_U8 = 1, KMP_CODER_U16 = 2, KMP_CODER_U32 = 3,
+  /* Near-lossless coders for 8- / 16-bit samples (signed ones on M(x)).  With the caller's bound
+     max_error = d, 1 <= d <= 2^(W-1) - 1, step = 2 d + 1 and P the prediction clamped to [0, 2^W - 1]
+     (a float32 prediction truncated first, NaN -> 0): the map holds q = sign(e) ((|e| + d) / step),
+     e = x - P, as W-bit two's complement in the unsigned map dtype, and the decode returns
+     clamp(P + q step, 0, 2^W - 1), within d of x.  Every ``int32_t coder`` argument that takes them
+     carries KMP_CODER_NEAR(code, d).  A lossless code with a max_error, a bound out of range or a width
+     that is not the samples' is KMP_ERR_ARG; 32-bit samples are KMP_ERR_UNSUPPORTED.  The fused
+     entry points serve them with the generic two-pass family alone. */
+  KMP_CODER_NEAR_U8 = 4, KMP_CODER_NEAR_U16 = 5
+} kmp_coder;
+#define KMP_CODER_NEAR(code, max_error) ((code) | ((max_error) << 8))
 typedef enum { KMP_ENCODE = 0, KMP_DECODE = 1 } kmp_direction;
 
 typedef enum {
@@ -247,7 +259,12 @@ int kmp_tiles(int32_t nsp, int32_t dtype, int32_t direction, const void* src, co
    dtypes (x = gt for ENCODE, encoded for DECODE); the output is uint8 / uint16 / int32 /
    uint32 for KMP_CODER_U8 / U16 / RAW / U32.  KMP_I8 / KMP_I16 operands with KMP_CODER_U8 / U16:
    (gt - pred) mod 2^W of the signed values -- the same bits as the unsigned codes give, the sign
-   map cancels in the difference; a decode's output holds the signed sample's bit pattern. */
+   map cancels in the difference; a decode's output holds the signed sample's bit pattern.
+   Near coders (KMP_CODER_NEAR): ``x_dtype`` is the SAMPLE dtype in both directions -- KMP_U8 / KMP_U16 /
+   KMP_I8 / KMP_I16; a decode's residuals are the unsigned W-bit map, labelled with the samples' code,
+   which says whether they are signed -- and ``pred_dtype`` is that dtype or KMP_F32 (truncated, then
+   clamped to the sample type's range).  The output is the unsigned map (encode) or the samples'
+   bit patterns (decode). */
 int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* pred, int32_t x_dtype,
              const void* x, int64_t n, void* out, kmp_stream_t stream);
 
@@ -282,7 +299,9 @@ int kmp_decode_with_predictions(int32_t nsp, int32_t dtype, int32_t coder, const
 
 /* The two above with the prediction maps' dtype given separately: ``pred_dtype`` is the sample
    dtype or KMP_F32 -- a network's float32 output, which the reference's coders read as
-   jnp.int32(pred) (truncating; out-of-range saturates here), utils.py:28-55. */
+   jnp.int32(pred) (truncating; out-of-range saturates here), utils.py:28-55.  All four take the near
+   coders too (``coder`` = KMP_CODER_NEAR of the dtype's width): the lowres passes through, the maps
+   hold the quantised residuals, and a decode returns samples within max_error of the coded ones. */
 int kmp_encode_with_predictions_typed(int32_t nsp, int32_t dtype, int32_t coder, int32_t pred_dtype,
                                       const void* highres, int64_t B, const int64_t shape[3], int64_t C,
                                       const void* const preds[7], void* lowres_out, void* const maps_out[7],

@@ -31,6 +31,21 @@ lib = ctypes.CDLL(LIB_PATH)
 KMP_OK, KMP_ERR_ARG, KMP_ERR_UNSUPPORTED, KMP_ERR_LAUNCH = 0, -1, -2, -3
 U8, U16, I32, F32, U32, I8, I16 = 0, 1, 2, 3, 4, 5, 6
 CODER_RAW, CODER_U8, CODER_U16, CODER_U32 = 0, 1, 2, 3
+CODER_NEAR_U8, CODER_NEAR_U16 = 4, 5  # near-lossless: the ``coder`` argument carries coder_near(code, max_error)
+
+
+def coder_near(code, max_error):
+    """KMP_CODER_NEAR(code, max_error): the value an ``int32_t coder`` argument carries."""
+    return int(code) | (int(max_error) << 8)
+
+
+def coder_code(coder):
+    return int(coder) & 0xff
+
+
+def coder_max_error(coder):
+    return int(coder) >> 8
+
 ENCODE, DECODE = 0, 1
 PRED_MEAN, PRED_LINEAR, PRED_LINEAR_MFMA = 0, 1, 2
 

@@ -23,10 +23,38 @@ PARITY = {
 }
 NMAPS = {3: 7, 2: 3}
 NPRED = {3: 19, 2: 5}
-CODER_DTYPE = {_lib.CODER_RAW: torch.int32, _lib.CODER_U8: torch.uint8, _lib.CODER_U16: torch.uint16,
-               _lib.CODER_U32: torch.uint32}
+
+
+class _CoderDtype(dict):
+    """The map dtype of a ``coder`` argument: keyed by the kmp_coder, and a near-lossless argument
+    (``_lib.coder_near(code, max_error)``) answers as its code does."""
+
+    def __missing__(self, coder):
+        code = _lib.coder_code(coder)
+        if code == coder or code not in NEAR_WIDTH:
+            raise KeyError(coder)
+        return self[code]
+
+
+NEAR_WIDTH = {_lib.CODER_NEAR_U8: 1, _lib.CODER_NEAR_U16: 2}  # the near coders' sample width, bytes
+CODER_DTYPE = _CoderDtype({_lib.CODER_RAW: torch.int32, _lib.CODER_U8: torch.uint8, _lib.CODER_U16: torch.uint16,
+                           _lib.CODER_U32: torch.uint32, _lib.CODER_NEAR_U8: torch.uint8,
+                           _lib.CODER_NEAR_U16: torch.uint16})
 NATURAL_CODER = {torch.uint8: _lib.CODER_U8, torch.uint16: _lib.CODER_U16, torch.int32: _lib.CODER_RAW,
                  torch.uint32: _lib.CODER_U32, torch.int8: _lib.CODER_U8, torch.int16: _lib.CODER_U16}
+
+
+def is_near(coder):
+    return _lib.coder_code(coder) in NEAR_WIDTH and _lib.coder_max_error(coder) > 0
+
+
+def coder_fits(coder, dtype):
+    """``coder`` is the one the fused kernels run for samples of ``dtype``: its natural lossless
+    coder, or the near-lossless coder of its width (8- / 16-bit integer samples)."""
+    if is_near(coder):
+        return dtype in (torch.uint8, torch.uint16, torch.int8, torch.int16) and \
+            NEAR_WIDTH[_lib.coder_code(coder)] == dtype.itemsize
+    return NATURAL_CODER.get(dtype) == coder
 
 
 def _sp(shape, nsp):
@@ -304,13 +332,16 @@ def d_trim_maps(maps, dims, nsp):
 # Coders
 # ---------------------------------------------------------------------------------------------
 
-def d_code(direction, coder, pred, x):
+def d_code(direction, coder, pred, x, x_code=None):
+    """``x_code``: the dtype code ``x`` is labelled with when it is not the tensor's own (a near
+    decode's residual map carries the sample dtype's code, which says whether the samples are signed)."""
     pred, x = _dev(pred), _dev(x)
     _require(tuple(pred.shape) == tuple(x.shape),
              f'coder operands must have equal shapes, got {tuple(pred.shape)} and {tuple(x.shape)}')
     out = dev.empty(x.shape, CODER_DTYPE[coder])
     if x.numel():
-        check(lib.kmp_code(direction, coder, dev.dtype_code(pred), pred.data_ptr(), dev.dtype_code(x), x.data_ptr(),
+        check(lib.kmp_code(direction, coder, dev.dtype_code(pred), pred.data_ptr(),
+                           dev.dtype_code(x) if x_code is None else x_code, x.data_ptr(),
                            x.numel(), out.data_ptr(), dev.stream()), 'code')
     return out
 
@@ -344,7 +375,7 @@ def fused_plan(predictions_fn, code_fn, padding, dtype, nsp, direction):
         return None
     if kmp_code[1] != direction or predictions_fn.padding != padding or predictions_fn.ndim != nsp:
         return None
-    if NATURAL_CODER.get(dtype) != kmp_code[0]:
+    if not coder_fits(kmp_code[0], dtype):
         return None
     return predictions_fn, kmp_code[0]
 
@@ -355,7 +386,7 @@ def callback_coder(code_fn, dtype, direction):
     if not fused_enabled():
         return None
     kc = getattr(code_fn, '_kmp_coder', None)
-    if kc is None or kc[1] != direction or NATURAL_CODER.get(dtype) != kc[0]:
+    if kc is None or kc[1] != direction or not coder_fits(kc[0], dtype):
         return None
     return kc[0]
 

@@ -42,8 +42,8 @@ import numpy as np
 import torch
 
 from . import _device as dev
-from . import _nd, packing
-from ._lib import check as _check, lib
+from . import _nd, near, packing
+from ._lib import check as _check, coder_max_error as _lib_max_error, lib
 from .predictors import ARITH_REV, LinearPredictor, MeanPredictor
 
 # wall-time split (seconds) of the last compress / decompress / save / load of this process
@@ -51,6 +51,10 @@ last_timing = {}
 
 MAGIC = b'KMPF'
 VERSION = 3  # 2: rice payloads are v2 bundles (packing.py); 3: a LinearPredictor's arith_rev recorded
+# 4: a near-lossless file: the metadata's 'max_error' > 0 is the bound its maps were
+# quantised with.  Only such files carry it, so lossless files stay version 3, byte for byte, and a
+# build from before near-lossless coding refuses a version-4 file instead of decoding it as lossless.
+VERSION_NEAR = 4
 _HEAD = struct.Struct('<4sHHQ')
 _NP_NAME = {torch.uint8: 'uint8', torch.uint16: 'uint16', torch.int32: 'int32', torch.uint32: 'uint32',
             torch.float32: 'float32', torch.int8: 'int8', torch.int16: 'int16'}
@@ -68,6 +72,29 @@ def _check_sample_dtype(meta, path):
         if name is not None and name not in _SAMPLE_NAMES:
             raise ValueError(f'{path}: {key} {name!r} is not a sample dtype this build knows '
                              f'({", ".join(sorted(_SAMPLE_NAMES))}): read it with the build that wrote it')
+
+
+def _check_max_error(meta, version, path):
+    """A version-4 file states its bound, in range for its sample dtype; no other version has one."""
+    delta = meta.get('max_error') if isinstance(meta, dict) else None
+    if version != VERSION_NEAR:
+        if delta not in (None, 0) or isinstance(delta, bool):
+            raise ValueError(f'{path}: a version-{version} file with max_error {delta!r} (near-lossless files are '
+                             f'version {VERSION_NEAR})')
+        return
+    name = meta.get('sample_dtype') or meta.get('lowres_dtype')
+    try:
+        if isinstance(delta, bool) or not isinstance(delta, int) or delta < 1:
+            raise ValueError(f'max_error {delta!r}')
+        near.check_max_error(name, delta)
+    except (ValueError, TypeError) as e:
+        raise ValueError(f'{path}: a version-{VERSION_NEAR} (near-lossless) file with a bad bound for {name!r} '
+                         f'samples: {e}') from None
+
+
+def _max_error(meta):
+    """The bound of a file whose header ``_read_head`` accepted (0: lossless)."""
+    return int(meta.get('max_error') or 0)
 
 
 def _predictor_meta(predictor, padding, ndim, dtype):
@@ -163,7 +190,7 @@ def _bundle(x, arrays, dims, method, tile_crc=False):
     return blob, blob.numel(), int(crc.cpu().view(torch.uint32).item()), None
 
 
-def _write(path, meta, blob, total, crc, t0, table=None):
+def _write(path, meta, blob, total, crc, t0, table=None, version=VERSION):
     """Header, metadata and the first ``total`` device bytes of ``blob`` to ``path``: the bundle
     crosses the link in pinned chunks (``_device.d2h_stream``), each written to the file while the
     next ones are in flight.  ``table`` (the per-tile CRCs, u32 little-endian) follows the bundle,
@@ -182,7 +209,7 @@ def _write(path, meta, blob, total, crc, t0, table=None):
             os.posix_fallocate(f.fileno(), 0, _HEAD.size + len(js) + total + len(trailer))  # 112 MB, write_probe_r5w2.log)
         except OSError:
             pass  # a filesystem without fallocate: the writes allocate
-        f.write(_HEAD.pack(MAGIC, VERSION, 0, len(js)))
+        f.write(_HEAD.pack(MAGIC, version, 0, len(js)))
         f.write(js)
         if total:
             dev.d2h_stream(blob[:total], lambda lo, piece: f.write(memoryview(piece)))
@@ -210,27 +237,37 @@ def _check_tile_crc_method(tile_crc, method):
 
 
 def save(path, lowres, encoded, predictor=None, padding=None, ndim=None, method='rice', sample_dtype=None,
-         tile_crc=False):
+         tile_crc=False, max_error=0):
     """Write an ``encode`` result ``(lowres, (maps, dims))`` to ``path``; returns the file size.
     ``predictor`` is recorded so :func:`decompress` can decode without being told.  ``padding``
     defaults to a built-in predictor's own padding (0 for an external predictions_fn).
     ``tile_crc=True`` (``method='rice'``) appends the per-tile CRC table :func:`read_region` checks
-    the tiles it touches against."""
+    the tiles it touches against.  ``max_error > 0``: ``encoded`` was made with
+    ``near.coders(dtype, max_error)``; the bound is recorded and the file is version 4 (the samples
+    are not at hand here, so the bound itself is checked where they are: :func:`compress`, or the
+    caller's own decode)."""
     maps, dims = encoded
     ndim = ndim or len(dims)
     padding = _builtin_padding(predictor, padding)
+    near.check_max_error(near._input_dtype(lowres), max_error)  # before the device is touched
     t0 = time.perf_counter()
     packing._check_method(method)
     _check_tile_crc_method(tile_crc, method)
     lo_t = dev.to_device(lowres)[0]
     maps_t = [dev.to_device(m)[0] for m in maps]
+    if max_error:
+        want = _nd.CODER_DTYPE[near.coder_id(lo_t.dtype, max_error)]
+        if any(m.dtype != want for m in maps_t):
+            raise TypeError(f'near-lossless maps of {lo_t.dtype} samples are {want}')
     meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'dims': [int(d) for d in dims],
             'method': method, 'lowres_shape': list(lo_t.shape), 'lowres_dtype': _NP_NAME[lo_t.dtype],
             'map_dtype': _NP_NAME[maps_t[0].dtype],
             'sample_dtype': sample_dtype or _NP_NAME[lo_t.dtype],
             'predictor': _predictor_meta(predictor, padding, ndim, lo_t.dtype) if predictor is not None else None}
+    if max_error:
+        meta['max_error'] = int(max_error)
     blob, total, crc, table = _bundle(lo_t, maps_t, dims, method, tile_crc)
-    return _write(path, meta, blob, total, crc, t0, table)
+    return _write(path, meta, blob, total, crc, t0, table, VERSION_NEAR if max_error else VERSION)
 
 
 def _read_head(f, path):
@@ -240,7 +277,7 @@ def _read_head(f, path):
     if len(head) < _HEAD.size:
         raise ValueError(f'{path}: not a kompressor_amd file (too short)')
     magic, version, _, mlen = _HEAD.unpack(head)
-    if magic != MAGIC or version not in (1, 2, VERSION) or mlen > (1 << 26):
+    if magic != MAGIC or version not in (1, 2, VERSION, VERSION_NEAR) or mlen > (1 << 26):
         raise ValueError(f'{path}: not a kompressor_amd file (magic {magic!r}, version {version})')
     try:
         meta = json.loads(f.read(mlen).decode())
@@ -248,6 +285,7 @@ def _read_head(f, path):
     except (ValueError, KeyError, TypeError) as e:
         raise ValueError(f'{path}: corrupt metadata ({e})') from None
     _check_sample_dtype(meta, path)
+    _check_max_error(meta, version, path)
     if version == 1 and meta.get('method') != 'planes':
         # version-1 'rice' payloads were the per-array KMPR format, replaced by the v2 bundle;
         # version-1 'planes' payloads are unchanged and still read
@@ -361,7 +399,7 @@ def _auto_levels(shape, ndim, max_levels=4):
     return max(levels, 1)
 
 
-def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False):
+def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0):
     """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
     :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int8 / int16
     modular on the sign-mapped samples, int32 raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
@@ -369,12 +407,19 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
     level's lowres, so only the coarsest lowres is stored raw -- entropy-code every array and write
     ``path``.  Returns ``{'bytes', 'raw_bytes', 'ratio', 'bits_per_sample', 'levels'}``.
     ``tile_crc=True`` (``method='rice'``) appends one CRC-32 per tile of 16384 samples, computed on the
-    device right after the encode, so :func:`read_region` verifies exactly the tiles it reads."""
+    device right after the encode, so :func:`read_region` verifies exactly the tiles it reads.
+    ``max_error = d > 0`` (uint8 / uint16 / int8 / int16 samples): near-lossless -- the closed loop of
+    ``near.encode_pyramid``, every restored sample within ``d`` of the original, which is checked on
+    the device before anything is written (a failed check raises and writes nothing); the file is
+    version 4 and the result also holds ``'max_error'`` and the measured ``'max_abs_error'``."""
+    near.check_max_error(near._input_dtype(highres), max_error)  # before the device is touched
     t0 = time.perf_counter()
     packing._check_method(method)
     _check_tile_crc_method(tile_crc, method)
     ndim, padding = predictor.ndim, predictor.padding
     h, _ = dev.to_device(highres)
+    if max_error:
+        return _compress_near(path, h, predictor, levels, method, tile_crc, int(max_error), t0)
     sample = _NP_NAME[h.dtype]
     if h.dtype == torch.float32:
         h = h.view(torch.uint32)
@@ -401,7 +446,32 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
     nbytes = _write(path, meta, blob, total, crc, t0, table)
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
-            'levels': levels}
+            'levels': levels, 'max_error': 0, 'max_abs_error': 0}
+
+
+def _compress_near(path, h, predictor, levels, method, tile_crc, max_error, t0):
+    """:func:`compress` with ``max_error > 0``: the closed loop, the bound's check, the version-4 file."""
+    ndim, padding = predictor.ndim, predictor.padding
+    levels = _auto_levels(h.shape, ndim) if levels == 'auto' else int(levels)
+    _nd._require(levels >= 1, 'levels must be >= 1')
+    lowres, encoded, restored = near.d_encode_pyramid(predictor, h, levels, near.coder_id(h.dtype, max_error))
+    worst = near.d_max_abs_error(restored, h)
+    if worst > max_error:
+        raise RuntimeError(f'near-lossless encode broke its bound: max |restored - highres| = {worst} > max_error = '
+                           f'{max_error}; nothing written to {path}')
+    arrays, meta_levels, shape = [], [], list(h.shape)
+    for maps, dims in encoded:
+        arrays.extend(maps)
+        meta_levels.append({'highres_shape': list(shape), 'dims': [int(d) for d in dims]})
+        shape = [shape[0], *[(s + 1) // 2 for s in shape[1:1 + ndim]], *shape[1 + ndim:]]
+    meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'method': method,
+            'sample_dtype': _NP_NAME[h.dtype], 'levels': meta_levels, 'lowres_shape': list(lowres.shape),
+            'predictor': _predictor_meta(predictor, padding, ndim, h.dtype), 'max_error': max_error}
+    blob, total, crc, table = _bundle(lowres, arrays, (), method, tile_crc)
+    nbytes = _write(path, meta, blob, total, crc, t0, table, VERSION_NEAR)
+    raw = h.numel() * h.element_size()
+    return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
+            'levels': levels, 'max_error': max_error, 'max_abs_error': worst}
 
 
 def _decode_predictor(path, meta, predictor, dtype):
@@ -441,8 +511,8 @@ def decompress(path, predictor=None, as_numpy=True):
     levels = meta.get('levels') or [{'dims': list(bundle_dims)}]  # save(): one level, dims in the bundle
     if len(arrays) != nmaps * len(levels):
         raise ValueError(f'{path}: {len(arrays)} coded maps for {len(levels)} levels of {nmaps}')
-    coder = _nd.NATURAL_CODER[lowres.dtype]
-    dec_fn = _coder_fn(coder, ndim)
+    coder = near.coder_id(lowres.dtype, _max_error(meta))  # the natural lossless coder, or the file's near coder
+    dec_fn = _coder_fn(coder, ndim, lowres.dtype)
     x = lowres
     for lvl in reversed(range(len(levels))):
         maps = list(arrays[nmaps * lvl:nmaps * (lvl + 1)])
@@ -466,8 +536,10 @@ def decompress(path, predictor=None, as_numpy=True):
     return out
 
 
-def _coder_fn(coder, ndim):
+def _coder_fn(coder, ndim, dtype=None):
     from . import utils
+    if _nd.is_near(coder):
+        return near.coders(dtype, _lib_max_error(coder))[1]
     name = {0: 'decode_values_raw', 1: 'decode_values_uint8', 2: 'decode_values_uint16', 3: 'decode_values_uint32'}
     return getattr(utils, name[coder])
 
@@ -508,6 +580,8 @@ def info(path):
                'ndim': int(meta['ndim']), 'levels': len(shapes), 'padding': int(meta['padding']),
                'predictor': pred.get('kind'), 'method': meta.get('method'), 'version': version,
                'file_bytes': int(size), 'bundle_bytes': int(n)}
+        if _max_error(meta):  # only a near-lossless file reports a bound
+            out['max_error'] = _max_error(meta)
         trailer = _tile_crc_trailer(meta, n, size - (_HEAD.size + mlen), path)
         if trailer is not None:  # only a file that has a table reports one
             out['tile_crc'] = trailer[1]
@@ -950,8 +1024,8 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
     # slab alone where the cross-section is whole, else the box) on its local arrays ----
     ndim, padding = meta['ndim'], meta['padding']
     nmaps = _nd.NMAPS[ndim]
-    coder = _nd.NATURAL_CODER[dtype]
-    dec_fn = _coder_fn(coder, ndim)
+    coder = near.coder_id(dtype, _max_error(meta))
+    dec_fn = _coder_fn(coder, ndim, dtype)
     x = local[0]
     for L in reversed(plan['levels']):
         lvl, ax = L['index'], L['axes']

@@ -477,6 +477,75 @@ __global__ void __launch_bounds__(kThreads) decode_preds_kernel(const T* __restr
   }
 }
 
+// The coder pass with a near-lossless coder (kmp_common.h), either direction, any channel count, one
+// output position and channel per thread.  TO: the unsigned type of the samples' width, which holds
+// samples and residuals alike; SGN: the samples are signed, so samples and sample-dtype predictions
+// go through M and a decode stores M^-1 of its result; a float32 prediction is truncated and clamped
+// to the sample type's own range.  The lowres nodes pass through unchanged.
+template <int CODER, bool DEC, bool SGN, typename P>
+__global__ void __launch_bounds__(kThreads) near_preds_kernel(const typename coder_out<CODER>::type* __restrict__ src,
+                                                            CMapPtrs maps_in, MapPtrs maps_out, CMapPtrs preds,
+                                                            typename coder_out<CODER>::type* __restrict__ dst, Geo g,
+                                                            int nsp, int64_t C, int64_t total, NearQ q) {
+  using TO = typename coder_out<CODER>::type;
+  constexpr int32_t MAX = (int32_t)std::numeric_limits<TO>::max();
+  constexpr int32_t HALF = SGN ? (MAX + 1) / 2 : 0;
+  const int nmaps = nsp == 3 ? 7 : 3;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+    int64_t b, oz, oy, ox, c;
+    unflat5(t, g.E[0], g.E[1], g.E[2], C, b, oz, oy, ox, c);
+    auto hidx = [&](int pz, int py, int px) -> int64_t {
+      return (((b * g.n[0] + 2 * oz + pz) * g.n[1] + 2 * oy + py) * g.n[2] + 2 * ox + px) * C + c;
+    };
+    if constexpr (DEC) dst[hidx(0, 0, 0)] = src[t];
+    else dst[t] = src[hidx(0, 0, 0)];
+    for (int k = 0; k < nmaps; ++k) {
+      int par[3];
+      map_parity(nsp, k, par);
+      int64_t u[3], e[3];
+      map_ext(g, nsp, k, u, e);
+      if (oz >= e[0] || oy >= e[1] || ox >= e[2]) continue;
+      const P pv = ((const P*)preds.p[k])[(((b * u[0] + oz) * u[1] + oy) * u[2] + ox) * C + c];
+      int32_t p;
+      if constexpr (std::is_same<P, float>::value) {
+        p = to_i32(pv);
+        p = p < -HALF ? 0 : (p > MAX - HALF ? MAX : p + HALF);
+      } else {
+        p = (int32_t)(TO)(pv ^ (TO)HALF);
+      }
+      const int64_t midx = (((b * e[0] + oz) * e[1] + oy) * e[2] + ox) * C + c;
+      const int64_t h = hidx(par[0], par[1], par[2]);
+      if constexpr (DEC)
+        dst[h] = (TO)(coder_dec<CODER>(q, p, (int32_t)((const TO*)maps_in.p[k])[midx]) ^ (TO)HALF);
+      else
+        ((TO*)maps_out.p[k])[midx] = coder_enc<CODER>(q, p, (int32_t)(TO)(src[h] ^ (TO)HALF));
+    }
+  }
+}
+
+// launch of the above for a checked near request (check_coder_arg: the coder's width is the dtype's)
+template <bool DEC>
+static int near_launch(int dtype, int32_t coder, int pred_dtype, const void* src, CMapPtrs maps_in, MapPtrs maps_out,
+                       CMapPtrs preds, void* dst, const Geo& g, int nsp, int64_t C, int64_t total, hipStream_t stream) {
+  if (pred_dtype != dtype && pred_dtype != KMP_F32)
+    return fail(KMP_ERR_UNSUPPORTED, "prediction maps must have the sample dtype or float32; got dtype " +
+                                         std::to_string(pred_dtype));
+  const NearQ q = make_nearq(coder_max_error(coder));
+  const bool sgn = dtype == KMP_I8 || dtype == KMP_I16, pf = pred_dtype == KMP_F32;
+  auto go = [&](auto coder_c, auto sgn_c, auto ptag) {
+    constexpr int CODER = decltype(coder_c)::value;
+    using TO = typename coder_out<CODER>::type;
+    using P = std::conditional_t<std::is_same<decltype(ptag), float>::value, float, TO>;
+    near_preds_kernel<CODER, DEC, decltype(sgn_c)::value, P><<<grid_for(total), kThreads, 0, stream>>>(
+        (const TO*)src, maps_in, maps_out, preds, (TO*)dst, g, nsp, C, total, q);
+    return check_launch(DEC ? "decode_with_predictions" : "encode_with_predictions");
+  };
+  auto with_p = [&](auto coder_c, auto sgn_c) { return pf ? go(coder_c, sgn_c, float{}) : go(coder_c, sgn_c, int{}); };
+  auto with_s = [&](auto coder_c) { return sgn ? with_p(coder_c, std::true_type{}) : with_p(coder_c, std::false_type{}); };
+  return coder_code(coder) == KMP_CODER_NEAR_U8 ? with_s(std::integral_constant<int, KMP_CODER_NEAR_U8>{})
+                                                : with_s(std::integral_constant<int, KMP_CODER_NEAR_U16>{});
+}
+
 template <typename F>
 static int dispatch_coder(int dtype, int coder, F&& f) {  // the built-in coder of each sample dtype
   if (dtype == KMP_U8 && coder == KMP_CODER_U8) return f(uint8_t{}, std::integral_constant<int, KMP_CODER_U8>{});
@@ -565,15 +634,19 @@ int kmp_encode_with_predictions_typed(int32_t nsp, int32_t dtype, int32_t coder,
   KMP_REQUIRE(nsp == 2 || nsp == 3, "nsp must be 2 or 3");
   KMP_REQUIRE(highres && shape && preds && lowres_out && maps_out && B >= 0 && C >= 1, "bad argument");
   for (int a = 0; a < nsp; ++a) KMP_REQUIRE(shape[a] >= 2, "spatial dims must be >= 2");
-  // signed samples: sample-dtype or float32 predictions code the same bits mod 2^W (kmp_common.h)
-  if (pred_dtype == dtype) pred_dtype = unsigned_twin(dtype);
-  dtype = unsigned_twin(dtype);
+  if (int st = check_coder_arg(coder, dtype_size(dtype), "encode_with_predictions")) return st;
   const Geo g = make_geo_from_highres(nsp, shape);
   CMapPtrs pp{};
   MapPtrs mp{};
   KMP_REQUIRE(bind_maps(nsp, preds, pp) && bind_maps(nsp, maps_out, mp), "null map pointer");
   const int64_t total = B * g.E[0] * g.E[1] * g.E[2] * C;
   if (total == 0) return KMP_OK;
+  if (is_near_code(coder_code(coder)))  // the signed dtypes keep their codes: the near coders work on M(x)
+    return cb::near_launch<false>(dtype, coder, pred_dtype, highres, CMapPtrs{}, mp, pp, lowres_out, g, nsp, C, total,
+                                  (hipStream_t)stream);
+  // signed samples: sample-dtype or float32 predictions code the same bits mod 2^W (kmp_common.h)
+  if (pred_dtype == dtype) pred_dtype = unsigned_twin(dtype);
+  dtype = unsigned_twin(dtype);
   const bool small = C == 1 && B * g.n[0] * g.n[1] * g.n[2] < ((int64_t)1 << 31) &&
                      B * g.L[0] * g.L[1] * g.L[2] < ((int64_t)1 << 31);
   return cb::dispatch_coder(dtype, coder, [&](auto tag, auto coder_c) {
@@ -621,13 +694,17 @@ int kmp_decode_with_predictions_typed(int32_t nsp, int32_t dtype, int32_t coder,
     KMP_REQUIRE(dims[a] == 0 || dims[a] == 1, "dims must be 0 or 1");
     KMP_REQUIRE(shape[a] >= 1 && shape[a] + dims[a] >= 2, "lowres too small");
   }
-  if (pred_dtype == dtype) pred_dtype = unsigned_twin(dtype);  // signed samples: as the encode
-  dtype = unsigned_twin(dtype);
+  if (int st = check_coder_arg(coder, dtype_size(dtype), "decode_with_predictions")) return st;
   const Geo g = make_geo_from_lowres(nsp, shape, dims);
   CMapPtrs pp{}, mp{};
   KMP_REQUIRE(bind_maps(nsp, preds, pp) && bind_maps(nsp, maps, mp), "null map pointer");
   const int64_t total = B * g.E[0] * g.E[1] * g.E[2] * C;
   if (total == 0) return KMP_OK;
+  if (is_near_code(coder_code(coder)))
+    return cb::near_launch<true>(dtype, coder, pred_dtype, lowres, mp, MapPtrs{}, pp, highres_out, g, nsp, C, total,
+                                 (hipStream_t)stream);
+  if (pred_dtype == dtype) pred_dtype = unsigned_twin(dtype);  // signed samples: as the encode
+  dtype = unsigned_twin(dtype);
   const bool small = C == 1 && B * g.n[0] * g.n[1] * g.n[2] < ((int64_t)1 << 31) &&
                      B * g.L[0] * g.L[1] * g.L[2] < ((int64_t)1 << 31);
   return cb::dispatch_coder(dtype, coder, [&](auto tag, auto coder_c) {

@@ -37,6 +37,7 @@ struct CodecCall {
   void* ws;
   size_t ws_bytes;
   hipStream_t stream;
+  int32_t max_error = 0;  // > 0: the near-lossless coder of T's width with this bound (generic family only)
 };
 
 // The coder of a request is the natural coder of its sample type (the front door admits no other
@@ -49,6 +50,12 @@ template <> struct natural_coder<int32_t> { static constexpr int value = KMP_COD
 template <> struct natural_coder<uint32_t> { static constexpr int value = KMP_CODER_U32; };
 template <> struct natural_coder<i8s> { static constexpr int value = KMP_CODER_U8; };
 template <> struct natural_coder<i16s> { static constexpr int value = KMP_CODER_U16; };
+
+// the near-lossless coder of an 8- / 16-bit sample type (KMP_CODER_NEAR(code, max_error) requests)
+template <typename T> struct near_coder {
+  static_assert(sizeof(T) <= 2, "near coders: 8- / 16-bit samples");
+  static constexpr int value = sizeof(T) == 1 ? KMP_CODER_NEAR_U8 : KMP_CODER_NEAR_U16;
+};
 
 // Kernel families, one per kmp_codec_<family>.hip.  Each returns KMP_ERR_UNSUPPORTED (without
 // touching anything) when the request is not eligible, and knows nothing of the others: the order

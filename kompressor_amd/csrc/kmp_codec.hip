@@ -4,9 +4,18 @@
 
 namespace kmp {
 
-// f(T{}) for a dtype with its natural coder (natural_coder, kmp_codec.h); nothing else is served
+// f(T{}) for a dtype with its natural coder (natural_coder, kmp_codec.h) or, for 8- / 16-bit samples,
+// the near-lossless coder of its width (near_coder; the bound travels in CodecCall); nothing else is served
 template <typename F>
 static int dispatch_natural(int dtype, int coder, F&& f) {
+  if (int st = check_coder_arg(coder, dtype_size(dtype), "fused codec")) return st;
+  if (is_near_code(coder_code(coder))) {  // the width matches the dtype's: checked
+    if (dtype == KMP_U8) return f(uint8_t{});
+    if (dtype == KMP_U16) return f(uint16_t{});
+    if (dtype == KMP_I8) return f(i8s{});
+    if (dtype == KMP_I16) return f(i16s{});
+    return fail(KMP_ERR_ARG, "fused codec: unsupported sample dtype " + std::to_string(dtype));
+  }
   if (dtype == KMP_U8 && coder == natural_coder<uint8_t>::value) return f(uint8_t{});
   if (dtype == KMP_U16 && coder == natural_coder<uint16_t>::value) return f(uint16_t{});
   if (dtype == KMP_I32 && coder == natural_coder<int32_t>::value) return f(int32_t{});
@@ -32,7 +41,11 @@ template <typename T, bool DEC>
 static int serve(const CodecCall<T, DEC>& c) {
   using Try = int (*)(const CodecCall<T, DEC>&);
   const Try* family;  // nullptr-terminated
-  if constexpr (sizeof(T) == 4) {
+  // a near-lossless request: the generic family alone has the quantising coder
+  static constexpr Try near[] = {try_generic<T, DEC>, nullptr};
+  if (c.max_error) {
+    family = near;
+  } else if constexpr (sizeof(T) == 4) {
     static constexpr Try volume[] = {try_wave3d32<T, DEC>, try_generic<T, DEC>, nullptr};
     static constexpr Try image[] = {try_generic<T, DEC>, nullptr};
     family = c.nsp == 3 ? volume : image;
@@ -99,7 +112,7 @@ int codec_encode(int nsp, int dtype, const void* highres, int64_t B, const int64
   return dispatch_natural(dtype, coder, [&](auto tag) {
     using T = decltype(tag);
     return serve(CodecCall<T, false>{nsp, g, B, C, pred, region, (const T*)highres, (T*)lowres_out,
-                                     maps, ws, ws_bytes, stream});
+                                     maps, ws, ws_bytes, stream, coder_max_error(coder)});
   });
 }
 
@@ -123,7 +136,7 @@ int codec_decode(int nsp, int dtype, const void* lowres, const void* const* maps
   return dispatch_natural(dtype, coder, [&](auto tag) {
     using T = decltype(tag);
     return serve(CodecCall<T, true>{nsp, g, B, C, pred, region, (const T*)lowres, (T*)highres_out,
-                                    maps, ws, ws_bytes, stream});
+                                    maps, ws, ws_bytes, stream, coder_max_error(coder)});
   });
 }
 

@@ -14,9 +14,11 @@
 // pad_lowres volume/utils.py:240-244); the neighbourhood padding adds sym(., L)
 // (pad_neighborhood volume/utils.py:213-218).  Costs ~1.25x the HBM bytes of the one-pass
 // fast kernels (kmp_codec_fast3d.hip); used whenever those are not eligible: the last entry of
-// every list of the dispatch table (kmp_codec.hip).  Here: the host side and the per-element
-// residual kernel; kmp_codec_generic_cells.hip is pass 1, kmp_codec_generic_row4.hip the residual
-// pass for up to 4 channels.
+// every list of the dispatch table (kmp_codec.hip), and the only entry of a near-lossless request's
+// (CodecCall::max_error > 0).  Here: the host side and the per-element residual
+// kernel (compiled once per coder family, below); kmp_codec_generic_cells.hip is pass 1,
+// kmp_codec_generic_row4.hip the residual pass for up to 4 channels.
+#ifndef KMP_PASS_KERNEL  // (this file includes its own kernel section, below)
 #include "kmp_generic.h"
 
 namespace kmp {
@@ -77,15 +79,18 @@ struct GenCells {
     return gcast<T>(s);
   }
 };
+#endif
 
+#ifdef KMP_PASS_KERNEL  // ---- the kernel section: KMP_PASS_KERNEL its name, KMP_PASS_PARAM what follows its
+// last parameter, KMP_PASS_ENC / KMP_PASS_DEC the coder's calls (defined where the section is included) ----
 // The residual pass, one thread per output position and channel: any channel count, 64-bit indices
 // when the arrays need them.  Encode reads highres ``src`` and writes lowres ``dst`` + ``omaps``;
 // decode reads lowres ``src`` + ``imaps`` and writes highres ``dst`` (the other maps stay unused).
 template <typename T, int CODER, bool PERCH, int NSP, typename I, bool DEC>
-__global__ void __launch_bounds__(kThreads) codec_generic_kernel(const T* __restrict__ src, CMapPtrs imaps, Geo g,
+__global__ void __launch_bounds__(kThreads) KMP_PASS_KERNEL(const T* __restrict__ src, CMapPtrs imaps, Geo g,
                                                                 int64_t B, int64_t C, const T* __restrict__ cells,
                                                                 int K, T* __restrict__ dst, MapPtrs omaps, Frame f,
-                                                                Flat F, int64_t total) {
+                                                                Flat F, int64_t total KMP_PASS_PARAM) {
   using TO = typename coder_out<CODER>::type;
   constexpr int NM = NSP == 3 ? 7 : 3;
   const I Cc = (I)C;
@@ -113,15 +118,38 @@ __global__ void __launch_bounds__(kThreads) codec_generic_kernel(const T* __rest
       const T pred = gc.pred(k);
       if constexpr (DEC) {
         const TO enc = ((const TO*)imaps.p[k])[((b * e0 + oz) * e1 + oy) * e2 * Cc + ox * Cc + c];
-        dst[h0 + p0 * hz + p1 * hy + p2 * Cc] = (T)code_decode<CODER>(to_i32(pred), to_i32(enc));
+        dst[h0 + p0 * hz + p1 * hy + p2 * Cc] = (T)KMP_PASS_DEC(to_i32(pred), to_i32(enc));
       } else {
         const T gt = src[h0 + p0 * hz + p1 * hy + p2 * Cc];
         ((TO*)omaps.p[k])[((b * e0 + oz) * e1 + oy) * e2 * Cc + ox * Cc + c] =
-            code_encode<CODER>(to_i32(pred), to_i32(gt));
+            KMP_PASS_ENC(to_i32(pred), to_i32(gt));
       }
     }
   }
 }
+
+#else  // ---- the whole file ----
+// The kernel above, compiled once per coder family by including this file's kernel section: the
+// modular coders (the token stream it always was), and the near-lossless coders (kmp_common.h) with
+// their bound as one more argument.
+#define KMP_PASS_KERNEL codec_generic_kernel
+#define KMP_PASS_PARAM
+#define KMP_PASS_ENC(p, x) code_encode<CODER>(p, x)
+#define KMP_PASS_DEC(p, e) code_decode<CODER>(p, e)
+#include "kmp_codec_generic.hip"
+#undef KMP_PASS_KERNEL
+#undef KMP_PASS_PARAM
+#undef KMP_PASS_ENC
+#undef KMP_PASS_DEC
+#define KMP_PASS_KERNEL codec_generic_near_kernel
+#define KMP_PASS_PARAM , NearQ nq
+#define KMP_PASS_ENC(p, x) coder_enc<CODER>(nq, p, x)
+#define KMP_PASS_DEC(p, e) coder_dec<CODER>(nq, p, e)
+#include "kmp_codec_generic.hip"
+#undef KMP_PASS_KERNEL
+#undef KMP_PASS_PARAM
+#undef KMP_PASS_ENC
+#undef KMP_PASS_DEC
 
 // Images with one channel and the f32 LinearPredictor at p <= 1: the row kernel computes its cells
 // itself (codec_row4_kernel FK > 0; at p = 2 the 7 x 10 node patch and 36 x 5 weights outgrow the
@@ -164,6 +192,14 @@ int try_generic(const CodecCall<T, DEC>& c) {
   const MapPtrs omaps = DEC ? MapPtrs{} : c.maps;
   with_nsp_perch(c.nsp, perch, [&](auto nsp_c, auto perch_c) {
     auto go = [&](auto i_tag) {
+      if constexpr (sizeof(T) <= 2) {
+        if (c.max_error) {
+          codec_generic_near_kernel<T, near_coder<T>::value, decltype(perch_c)::value, decltype(nsp_c)::value,
+                                    decltype(i_tag), DEC><<<grid_for(total), kThreads, 0, c.stream>>>(
+              c.in, imaps, g, c.B, c.C, cells, K, c.out, omaps, f, F, total, make_nearq(c.max_error));
+          return;
+        }
+      }
       codec_generic_kernel<T, natural_coder<T>::value, decltype(perch_c)::value, decltype(nsp_c)::value,
                            decltype(i_tag), DEC>
           <<<grid_for(total), kThreads, 0, c.stream>>>(c.in, imaps, g, c.B, c.C, cells, K, c.out, omaps, f, F, total);
@@ -181,3 +217,4 @@ KMP_INST_FAMILY(try_generic, uint32_t)
 KMP_INST_FAMILY_SIGNED(try_generic)
 
 }  // namespace kmp
+#endif

@@ -1,5 +1,6 @@
 // kmp_codec_generic_row4.hip -- pass 2 of the generic two-pass codec (kmp_codec_generic.hip) for up
 // to 4 interleaved channels: a thread owns 4 consecutive output columns of a row.
+#ifndef KMP_PASS_KERNEL  // (this file includes its own kernel section, below)
 #include "kmp_generic.h"
 
 namespace kmp {
@@ -67,7 +68,10 @@ __device__ __forceinline__ void g_storen(T* p, const uint32_t (&v)[N]) {
 struct Row4 {
   FDiv dq, d1, d0;
 };
+#endif
 
+#ifdef KMP_PASS_KERNEL  // ---- the kernel section: KMP_PASS_KERNEL its name, KMP_PASS_PARAM what follows its
+// last parameter, KMP_PASS_ENC / KMP_PASS_DEC the coder's calls (defined where the section is included) ----
 // CC channels (1..4, interleaved): a thread owns 4 output positions x CC channels of a row, so
 // its highres rows are 8 x CC consecutive samples, its lowres / map values 4 x CC, its cells 5 x CC
 // FK > 0 (images, one channel, f32 LinearPredictor with KK = FK = 2p + 2 <= 4): no cells array --
@@ -76,11 +80,11 @@ struct Row4 {
 // Each cell is computed by ~2.5 threads; the cells pass (a write and a re-read of 5 predictions a
 // cell) is gone.
 template <typename T, int CODER, bool PERCH, int NSP, int CC, bool DEC, int FK = 0>
-__global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restrict__ src, CMapPtrs imaps, Geo g,
+__global__ void __launch_bounds__(kThreads) KMP_PASS_KERNEL(const T* __restrict__ src, CMapPtrs imaps, Geo g,
                                                              const T* __restrict__ cells, int64_t B, T* __restrict__ dst,
                                                              MapPtrs omaps, Frame f, Row4 R, int64_t nxq,
                                                              int64_t total, Src ns = Src{}, const float* W = nullptr,
-                                                             const float* bias = nullptr, int p = 0) {
+                                                             const float* bias = nullptr, int p = 0 KMP_PASS_PARAM) {
   static_assert(FK == 0 || (NSP == 2 && CC == 1 && PERCH), "fused cells: images, one channel, LinearPredictor");
   constexpr int FKO = 5, FN = FK * FK;  // outputs / features of a 2D cell
   __shared__ float wl[FK > 0 ? FN * FKO + FKO : 1];
@@ -234,7 +238,7 @@ __global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restric
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int ch = 0; ch < CC; ++ch)
-            ov[i * CC + ch] = (uint32_t)code_encode<CODER>((int32_t)pred(k, i, ch),
+            ov[i * CC + ch] = (uint32_t)KMP_PASS_ENC((int32_t)pred(k, i, ch),
                                                            to_i32((TM)hv[NSP == 3 ? p0 : 0][p1][(2 * i + p2) * CC + ch]));
         TO* mp = (TO*)omaps.p[k] + (((b * e0 + oz) * e1 + oy) * e2 + ox0) * CC;
         if (n == 4) g_storen<TO, NO>(mp, ov);
@@ -290,7 +294,7 @@ __global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restric
 #pragma unroll
           for (int ch = 0; ch < CC; ++ch)
             hv[NSP == 3 ? p0 : 0][p1][2 * i + p2][ch] =
-                (uint32_t)(TM)code_decode<CODER>((int32_t)pred(k, i, ch), (int32_t)(TO)mv[i * CC + ch]);
+                (uint32_t)(TM)KMP_PASS_DEC((int32_t)pred(k, i, ch), (int32_t)(TO)mv[i * CC + ch]);
           hok[NSP == 3 ? p0 : 0][p1][2 * i + p2] = i < n;
         }
       }
@@ -319,6 +323,29 @@ __global__ void __launch_bounds__(kThreads) codec_row4_kernel(const T* __restric
   }
 }
 
+#else  // ---- the whole file ----
+// The kernel above, compiled once per coder family by including this file's kernel section: the
+// modular coders (the token stream it always was), and the near-lossless coders (kmp_common.h) with
+// their bound as one more argument.
+#define KMP_PASS_KERNEL codec_row4_kernel
+#define KMP_PASS_PARAM
+#define KMP_PASS_ENC(p, x) code_encode<CODER>(p, x)
+#define KMP_PASS_DEC(p, e) code_decode<CODER>(p, e)
+#include "kmp_codec_generic_row4.hip"
+#undef KMP_PASS_KERNEL
+#undef KMP_PASS_PARAM
+#undef KMP_PASS_ENC
+#undef KMP_PASS_DEC
+#define KMP_PASS_KERNEL codec_row4_near_kernel
+#define KMP_PASS_PARAM , NearQ nq = NearQ{}
+#define KMP_PASS_ENC(p, x) coder_enc<CODER>(nq, p, x)
+#define KMP_PASS_DEC(p, e) coder_dec<CODER>(nq, p, e)
+#include "kmp_codec_generic_row4.hip"
+#undef KMP_PASS_KERNEL
+#undef KMP_PASS_PARAM
+#undef KMP_PASS_ENC
+#undef KMP_PASS_DEC
+
 // the row kernel's compile-time channel count (1..4; 3D takes 1..2 -- with 3-4 channels its
 // 7 maps' values outgrow the registers and spill)
 template <typename F>
@@ -338,6 +365,15 @@ void launch_row4(const CodecCall<T, DEC>& c, const Src& s, const Frame& f, const
   const MapPtrs omaps = DEC ? MapPtrs{} : c.maps;
   if (!cells) {  // the cells computed in the kernel, FK = 2p + 2 nodes per axis (p <= 1)
     auto fused = [&](auto fk_c) {
+      if constexpr (sizeof(T) <= 2) {
+        if (c.max_error) {
+          codec_row4_near_kernel<T, near_coder<T>::value, true, 2, 1, DEC, decltype(fk_c)::value>
+              <<<grid_for(n4), kThreads, 0, c.stream>>>(c.in, imaps, c.g, nullptr, c.B, c.out, omaps, f, R, nxq, n4, s,
+                                                        c.pred->weights, c.pred->bias, c.pred->padding,
+                                                        make_nearq(c.max_error));
+          return;
+        }
+      }
       codec_row4_kernel<T, CODER, true, 2, 1, DEC, decltype(fk_c)::value><<<grid_for(n4), kThreads, 0, c.stream>>>(
           c.in, imaps, c.g, nullptr, c.B, c.out, omaps, f, R, nxq, n4, s, c.pred->weights, c.pred->bias,
           c.pred->padding);
@@ -349,9 +385,18 @@ void launch_row4(const CodecCall<T, DEC>& c, const Src& s, const Frame& f, const
   with_nsp_perch(c.nsp, c.pred->kind != KMP_PRED_MEAN, [&](auto nsp_c, auto perch_c) {
     with_cc(c.C, [&](auto cc_c) {
       constexpr int NSP = decltype(nsp_c)::value, CC = decltype(cc_c)::value;
-      if constexpr (NSP == 2 || CC <= 2)
+      if constexpr (NSP == 2 || CC <= 2) {
+        if constexpr (sizeof(T) <= 2) {
+          if (c.max_error) {
+            codec_row4_near_kernel<T, near_coder<T>::value, decltype(perch_c)::value, NSP, CC, DEC>
+                <<<grid_for(n4), kThreads, 0, c.stream>>>(c.in, imaps, c.g, cells, c.B, c.out, omaps, f, R, nxq, n4,
+                                                          Src{}, nullptr, nullptr, 0, make_nearq(c.max_error));
+            return;
+          }
+        }
         codec_row4_kernel<T, CODER, decltype(perch_c)::value, NSP, CC, DEC>
             <<<grid_for(n4), kThreads, 0, c.stream>>>(c.in, imaps, c.g, cells, c.B, c.out, omaps, f, R, nxq, n4);
+      }
     });
   });
 }
@@ -362,3 +407,4 @@ void launch_row4(const CodecCall<T, DEC>& c, const Src& s, const Frame& f, const
 KMP_FOR_SAMPLE_TYPES(KMP_INST_ROW4)
 
 }  // namespace kmp
+#endif

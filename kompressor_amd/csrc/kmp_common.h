@@ -306,6 +306,75 @@ __device__ __forceinline__ uint32_t udiv(uint32_t n, UDiv f) {
   return f.s < 0 ? n : __umulhi(n, f.m) >> f.s;
 }
 
+// ------------------------------------------------------------------------------------------
+// Near-lossless coders (KMP_CODER_NEAR_U8 / U16)
+// ------------------------------------------------------------------------------------------
+// The residual e = x - P of a sample against its prediction, clamped to [0, MAX], is quantised to
+// q = sign(e) ((|e| + delta) / step), step = 2 delta + 1, and stored as W-bit two's complement
+// (|q| <= (MAX + delta) / step < 2^(W-1)); the reconstruction is clamp(P + q step, 0, MAX), within
+// delta of x with no modular wrap.  Signed samples are coded on M(x), as everywhere.  The bound
+// reaches a kernel at run time in a NearQ; the modular coders carry no state (Lossless), so a
+// kernel body templated on the state compiles to what it was without one.
+template <> struct coder_out<KMP_CODER_NEAR_U8> { using type = uint8_t; };
+template <> struct coder_out<KMP_CODER_NEAR_U16> { using type = uint16_t; };
+template <int CODER> constexpr bool coder_is_near = CODER == KMP_CODER_NEAR_U8 || CODER == KMP_CODER_NEAR_U16;
+
+struct Lossless {};
+struct NearQ {
+  int32_t delta, step;
+  UDiv div;  // / step: exact below 2^31, and |e| + delta <= MAX + 2^(W-1) - 1 < 2^17
+};
+inline NearQ make_nearq(int32_t delta) { return NearQ{delta, 2 * delta + 1, make_udiv((uint32_t)(2 * delta + 1))}; }
+
+// the low byte of a C-ABI ``coder`` argument is the kmp_coder, the rest the near coders' max_error
+inline int coder_code(int32_t coder) { return coder & 0xff; }
+inline int32_t coder_max_error(int32_t coder) { return (int32_t)((uint32_t)coder >> 8); }
+inline bool is_near_code(int code) { return code == KMP_CODER_NEAR_U8 || code == KMP_CODER_NEAR_U16; }
+// KMP_OK for a well-formed ``coder`` argument whose sample width (bytes) is ``width``: a lossless
+// code carries no max_error; a near code's width is the samples' (1 / 2; none for 32-bit samples:
+// KMP_ERR_UNSUPPORTED) and 1 <= max_error <= 2^(W-1) - 1
+inline int check_coder_arg(int32_t coder, int width, const char* who) {
+  const int code = coder_code(coder);
+  const int32_t delta = coder_max_error(coder);
+  if (coder < 0 || code > KMP_CODER_NEAR_U16) return fail(KMP_ERR_ARG, std::string(who) + ": bad coder");
+  if (!is_near_code(code))
+    return delta ? fail(KMP_ERR_ARG, std::string(who) + ": a lossless coder takes no max_error") : KMP_OK;
+  if (width == 4) return fail(KMP_ERR_UNSUPPORTED, std::string(who) + ": no near-lossless coder for 32-bit samples");
+  if (width != (code == KMP_CODER_NEAR_U8 ? 1 : 2))
+    return fail(KMP_ERR_ARG, std::string(who) + ": the near coder's width does not match the sample dtype");
+  if (delta < 1 || delta > (1 << (8 * width - 1)) - 1)
+    return fail(KMP_ERR_ARG, std::string(who) + ": max_error " + std::to_string(delta) + " outside [1, 2^(W-1) - 1]");
+  return KMP_OK;
+}
+
+template <int CODER>
+__device__ __forceinline__ typename coder_out<CODER>::type coder_enc(Lossless, int32_t pred, int32_t gt) {
+  return code_encode<CODER>(pred, gt);
+}
+template <int CODER>
+__device__ __forceinline__ typename coder_out<CODER>::type coder_dec(Lossless, int32_t pred, int32_t enc) {
+  return code_decode<CODER>(pred, enc);
+}
+// ``gt`` in [0, MAX]; ``pred`` any int32 (an out-of-range float32 prediction, truncated)
+template <int CODER>
+__device__ __forceinline__ typename coder_out<CODER>::type coder_enc(const NearQ& q, int32_t pred, int32_t gt) {
+  constexpr int32_t MAX = (int32_t)((1u << (8 * sizeof(typename coder_out<CODER>::type))) - 1u);
+  const int32_t P = pred < 0 ? 0 : (pred > MAX ? MAX : pred);
+  const int32_t e = gt - P;
+  const int32_t k = (int32_t)udiv((uint32_t)((e < 0 ? -e : e) + q.delta), q.div);
+  return (typename coder_out<CODER>::type)(uint32_t)(e < 0 ? -k : k);
+}
+// ``enc``: the stored W bits (any extension above them)
+template <int CODER>
+__device__ __forceinline__ typename coder_out<CODER>::type coder_dec(const NearQ& q, int32_t pred, int32_t enc) {
+  constexpr int SH = 32 - 8 * (int)sizeof(typename coder_out<CODER>::type);
+  constexpr int32_t MAX = (int32_t)(0xffffffffu >> SH);
+  const int32_t P = pred < 0 ? 0 : (pred > MAX ? MAX : pred);
+  const int32_t k = (int32_t)((uint32_t)enc << SH) >> SH;
+  const int32_t r = P + k * q.step;  // |k| <= 2^(W-1), step < 2^W: no overflow
+  return (typename coder_out<CODER>::type)(r < 0 ? 0 : (r > MAX ? MAX : r));
+}
+
 // 16-byte vectors: aligned, and any-alignment (gfx950 serves unaligned dwordx4 global accesses;
 // rows of odd length are only element-aligned)
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));

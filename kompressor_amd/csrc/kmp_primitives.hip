@@ -233,6 +233,31 @@ __global__ void __launch_bounds__(kThreads) code_kernel(const TP* __restrict__ p
   }
 }
 
+// Near-lossless coders (kmp_common.h), one element per thread.  ``pred`` holds the sample dtype's bit
+// patterns or float32, ``x`` the samples (encode) or the stored W-bit residuals (decode); SGN: the
+// samples are signed, so samples and predictions are taken through M and a decode stores M^-1 of
+// its result.  A float32 prediction is truncated and clamped to the sample type's own range.
+template <int DIR, int CODER, bool SGN, typename TP>
+__global__ void __launch_bounds__(kThreads) code_near_kernel(const TP* __restrict__ pred,
+                                                           const typename coder_out<CODER>::type* __restrict__ x,
+                                                           int64_t n, typename coder_out<CODER>::type* __restrict__ out,
+                                                           NearQ q) {
+  using TO = typename coder_out<CODER>::type;
+  constexpr int32_t MAX = (int32_t)std::numeric_limits<TO>::max();
+  constexpr int32_t HALF = SGN ? (MAX + 1) / 2 : 0;
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+    int32_t p;
+    if constexpr (std::is_same<TP, float>::value) {
+      p = to_i32(pred[t]);
+      p = p < -HALF ? 0 : (p > MAX - HALF ? MAX : p + HALF);
+    } else {
+      p = (int32_t)(TO)(pred[t] ^ (TO)HALF);
+    }
+    if constexpr (DIR == KMP_ENCODE) out[t] = coder_enc<CODER>(q, p, (int32_t)(TO)(x[t] ^ (TO)HALF));
+    else out[t] = (TO)(coder_dec<CODER>(q, p, (int32_t)x[t]) ^ (TO)HALF);
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Box copy with conversion (slicing / .at[box].set of the chunk driver)
 // ------------------------------------------------------------------------------------------
@@ -631,6 +656,36 @@ int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* p
   if (n == 0) return KMP_OK;
   KMP_REQUIRE(pred && x && out, "null pointer");
   hipStream_t s = (hipStream_t)stream;
+  if (int st = check_coder_arg(coder, dtype_size(x_dtype), "kmp_code")) return st;
+  if (is_near_code(coder_code(coder))) {
+    // the samples' dtype is x's (a decode's residuals are labelled with it: the signed codes say
+    // "signed samples"); predictions are in that dtype or float32
+    KMP_REQUIRE(x_dtype == KMP_U8 || x_dtype == KMP_U16 || x_dtype == KMP_I8 || x_dtype == KMP_I16,
+                "near coders take 8- / 16-bit integer samples");
+    KMP_REQUIRE(pred_dtype == x_dtype || pred_dtype == KMP_F32, "near coders: predictions in the sample dtype or float32");
+    const NearQ q = make_nearq(coder_max_error(coder));
+    const bool sgn = x_dtype == KMP_I8 || x_dtype == KMP_I16, pf = pred_dtype == KMP_F32;
+    auto go = [&](auto dir_c, auto coder_c, auto sgn_c, auto ptag) {
+      constexpr int CODER = decltype(coder_c)::value;
+      using TO = typename coder_out<CODER>::type;
+      using TP = std::conditional_t<std::is_same<decltype(ptag), float>::value, float, TO>;
+      code_near_kernel<decltype(dir_c)::value, CODER, decltype(sgn_c)::value, TP>
+          <<<grid_for(n), kThreads, 0, s>>>((const TP*)pred, (const TO*)x, n, (TO*)out, q);
+      return check_launch("code");
+    };
+    auto with_p = [&](auto dir_c, auto coder_c, auto sgn_c) {
+      return pf ? go(dir_c, coder_c, sgn_c, float{}) : go(dir_c, coder_c, sgn_c, int{});
+    };
+    auto with_s = [&](auto dir_c, auto coder_c) {
+      return sgn ? with_p(dir_c, coder_c, std::true_type{}) : with_p(dir_c, coder_c, std::false_type{});
+    };
+    auto with_c = [&](auto dir_c) {
+      return coder_code(coder) == KMP_CODER_NEAR_U8 ? with_s(dir_c, std::integral_constant<int, KMP_CODER_NEAR_U8>{})
+                                                    : with_s(dir_c, std::integral_constant<int, KMP_CODER_NEAR_U16>{});
+    };
+    return direction == KMP_ENCODE ? with_c(std::integral_constant<int, KMP_ENCODE>{})
+                                   : with_c(std::integral_constant<int, KMP_DECODE>{});
+  }
   pred_dtype = unsigned_twin(pred_dtype);  // signed samples: the same bits mod 2^W (kmp_common.h)
   x_dtype = unsigned_twin(x_dtype);
   auto launch = [&](auto dir_c, auto coder_c) {

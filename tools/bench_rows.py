@@ -470,6 +470,49 @@ def main():
                 print(json.dumps(line), flush=True)
             del xu, xs, fns
 
+    # near-lossless coding, only when asked for: the generic family on 512 x 63^3
+    # uint16, MeanPredictor(0), the lossless coder against max_error = 2.  The two routes alternate
+    # within one process; each sample is the device-event time of ``reps`` back-to-back calls, and the
+    # line reports the median with min-max over the samples.  The lossless row is the yardstick.
+    if 'near' in want:
+        # every one-pass family off, so the lossless route is the generic kernel too
+        for name in ('KMP_DISABLE_WAVE', 'KMP_DISABLE_FAST'):
+            kom._lib.set_option(name, 1)
+        x63 = torch.from_numpy(rand((512, 63, 63, 63, 1), np.uint16, seed=3)).cuda()
+        pred = kom.MeanPredictor(0, 3)
+        raw = x63.numel() * 2
+        ws = torch.empty(max(1, _nd.workspace_bytes(x63, pred, 3)), dtype=torch.uint8, device='cuda')
+        routes = {}
+        for tag, coder in (('lossless', _nd.NATURAL_CODER[x63.dtype]), ('near2', kom.near.coder_id(torch.uint16, 2))):
+            lo, maps, dims = _nd._alloc_encoded(x63, coder, 3)
+            rec = torch.empty_like(x63)
+            fe = lambda c=coder, lo=lo, maps=maps: _nd.fused_encode_into(x63, pred, c, lo, maps, 3, workspace=ws)  # noqa: E731
+            fd = lambda c=coder, lo=lo, maps=maps, dims=dims, rec=rec: _nd.fused_decode_into(  # noqa: E731
+                lo, maps, dims, pred, c, rec, 3, workspace=ws)
+            fe()
+            assert kom._lib.lib.kmp_last_launch().decode() == 'encode_generic', tag
+            fd()
+            assert kom._lib.lib.kmp_last_launch().decode() == 'decode_generic', tag
+            torch.cuda.synchronize()
+            err = kom.near.d_max_abs_error(rec, x63)
+            assert err == (0 if tag == 'lossless' else 2), (tag, err)
+            routes[tag] = {'encode': fe, 'decode': fd}
+        samples = {(t, d): [] for t in routes for d in ('encode', 'decode')}
+        for _ in range(9):
+            for d in ('encode', 'decode'):
+                for t in routes:
+                    samples[(t, d)].append(gpu_time(routes[t][d], args.reps))
+        med = {k: float(np.median(v)) for k, v in samples.items()}
+        for (t, d), v in samples.items():
+            line = {'row': f'near:{t}:{d}', 'what': f'generic family, 512 x 63^3 uint16, {pred!r}',
+                    'GBps': round(2 * raw / med[(t, d)] / 1e9, 1), 'us': round(med[(t, d)] * 1e6, 1),
+                    'us_min': round(min(v) * 1e6, 1), 'us_max': round(max(v) * 1e6, 1), 'samples': len(v),
+                    'ratio_to_lossless': round(med[(t, d)] / med[('lossless', d)], 4)}
+            print(json.dumps(line), flush=True)
+        del x63, routes
+        for name in ('KMP_DISABLE_WAVE', 'KMP_DISABLE_FAST'):
+            kom._lib.set_option(name, None)
+
     # geometry primitives (volume/utils.py) on the C3 tile batch
     if not want or 'primitives' in want:
         hp, _ = _nd.d_pad_highres(vol, 3)                       # [512, 65^3]
