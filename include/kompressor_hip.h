@@ -55,9 +55,21 @@ typedef enum {
      carries KMP_CODER_NEAR(code, d).  A lossless code with a max_error, a bound out of range or a width
      that is not the samples' is KMP_ERR_ARG; 32-bit samples are KMP_ERR_UNSUPPORTED.  The fused
      entry points serve them with the generic two-pass family alone. */
-  KMP_CODER_NEAR_U8 = 4, KMP_CODER_NEAR_U16 = 5
+  KMP_CODER_NEAR_U8 = 4, KMP_CODER_NEAR_U16 = 5,
+  /* Error-bounded float32 quantisers (kmp_code alone).  The step is 2^e, -126 <= e <= 127,
+     and the ``coder`` argument carries KMP_CODER_QUANT(code, e).  With QMAX = 32767 (I16) or
+     2^31 - 1 (I32), all arithmetic in float64 (every operation is exact but the last conversion):
+       n = rint(x 2^-e) (ties to even),  r = (float)(n 2^e);
+       x is an exception iff x is not finite, |n| > QMAX, r is not finite or |r - x| > 2^(e-1).
+     ENCODE (x_dtype = KMP_F32) writes n as int16 / int32, an exception as the type's minimum
+     (-QMAX - 1, which no legal n takes); DECODE (x_dtype = KMP_I16 / KMP_I32, matching the code)
+     writes the float32 r of every element.  They take no prediction: ``pred`` must be NULL and
+     ``pred_dtype`` is not read.  A non-NULL pred, an exponent field of 0 or >= 255, an x_dtype that
+     does not fit, or these codes on any other entry point: KMP_ERR_ARG. */
+  KMP_CODER_QUANT_I16 = 6, KMP_CODER_QUANT_I32 = 7
 } kmp_coder;
 #define KMP_CODER_NEAR(code, max_error) ((code) | ((max_error) << 8))
+#define KMP_CODER_QUANT(code, exp) ((code) | (((exp) + 127) << 8))
 typedef enum { KMP_ENCODE = 0, KMP_DECODE = 1 } kmp_direction;
 
 typedef enum {
@@ -264,7 +276,9 @@ int kmp_tiles(int32_t nsp, int32_t dtype, int32_t direction, const void* src, co
    KMP_I8 / KMP_I16; a decode's residuals are the unsigned W-bit map, labelled with the samples' code,
    which says whether they are signed -- and ``pred_dtype`` is that dtype or KMP_F32 (truncated, then
    clamped to the sample type's range).  The output is the unsigned map (encode) or the samples'
-   bit patterns (decode). */
+   bit patterns (decode).
+   Quantisers (KMP_CODER_QUANT, see kmp_coder): ``pred`` is NULL; float32 -> int16 / int32 (ENCODE),
+   int16 / int32 -> float32 (DECODE). */
 int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* pred, int32_t x_dtype,
              const void* x, int64_t n, void* out, kmp_stream_t stream);
 

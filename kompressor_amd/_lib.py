@@ -39,6 +39,15 @@ def coder_near(code, max_error):
     return int(code) | (int(max_error) << 8)
 
 
+# error-bounded float32 quantisers (kmp_code alone): the argument carries coder_quant(code, exponent)
+CODER_QUANT_I16, CODER_QUANT_I32 = 6, 7
+
+
+def coder_quant(code, exp):
+    """KMP_CODER_QUANT(code, exp): the quantiser ``code`` with the step ``2**exp``."""
+    return int(code) | ((int(exp) + 127) << 8)
+
+
 def coder_code(coder):
     return int(coder) & 0xff
 

@@ -23,6 +23,8 @@ one CRC-32 per bundle tile (``meta['tile_crc'] = {'offset', 'tiles'}``, the offs
 start; ``packing.tile_crcs``): ``read_region`` verifies the tiles it touches against it, ``check``
 and a failing ``decompress`` name the damaged ones.  ``bundle_bytes`` and ``crc32`` cover the bundle
 alone either way, and a reader that does not know the key reads the file as before.
+Version 4 is a near-lossless file (``'max_error'``), version 5 an error-bounded float32 file
+(``'quant'``, and its exception arrays behind the maps); see ``VERSION_NEAR`` / ``VERSION_QUANT`` below.
 
 The host side of the file path (round 4): the bundle's CRC-32 (zlib's, the value the file stores)
 is computed on the device (``kmp_crc32``) -- over the bundle the encode just wrote, its length read
@@ -42,8 +44,8 @@ import numpy as np
 import torch
 
 from . import _device as dev
-from . import _nd, near, packing
-from ._lib import check as _check, coder_max_error as _lib_max_error, lib
+from . import _nd, near, packing, quant
+from ._lib import DECODE as _lib_decode, check as _check, coder_max_error as _lib_max_error, lib
 from .predictors import ARITH_REV, LinearPredictor, MeanPredictor
 
 # wall-time split (seconds) of the last compress / decompress / save / load of this process
@@ -55,6 +57,15 @@ VERSION = 3  # 2: rice payloads are v2 bundles (packing.py); 3: a LinearPredicto
 # quantised with.  Only such files carry it, so lossless files stay version 3, byte for byte, and a
 # build from before near-lossless coding refuses a version-4 file instead of decoding it as lossless.
 VERSION_NEAR = 4
+# 5: an error-bounded float32 file: 'sample_dtype' is 'float32', the levels and the lowres
+# are those of a lossless file of the int16 / int32 array ``quant.quantise`` made of it, and the metadata's
+# 'quant' = {'exp', 'dtype', 'exceptions': E} records the step 2^exp, that integer dtype and the number
+# of values kept as raw bits.  With E > 0 the bundle ends with three uint32 arrays of E entries: the low
+# and the high words of the gaps between consecutive sorted flat indices (the first gap is the first
+# index), and the bits.  Older builds refuse version 5.
+VERSION_QUANT = 5
+_QUANT_DTYPES = {'int16': torch.int16, 'int32': torch.int32}
+_QUANT_SLAB = 1 << 24  # elements per slab of the bound's check
 _HEAD = struct.Struct('<4sHHQ')
 _NP_NAME = {torch.uint8: 'uint8', torch.uint16: 'uint16', torch.int32: 'int32', torch.uint32: 'uint32',
             torch.float32: 'float32', torch.int8: 'int8', torch.int16: 'int16'}
@@ -90,6 +101,35 @@ def _check_max_error(meta, version, path):
     except (ValueError, TypeError) as e:
         raise ValueError(f'{path}: a version-{VERSION_NEAR} (near-lossless) file with a bad bound for {name!r} '
                          f'samples: {e}') from None
+
+
+def _check_quant(meta, version, path):
+    """A version-5 file is float32, states a well-formed 'quant' and carries no 'max_error'; no other
+    version has a 'quant'."""
+    q = meta.get('quant')
+    if version != VERSION_QUANT:
+        if q is not None:
+            raise ValueError(f'{path}: a version-{version} file with a quant entry (error-bounded files are version '
+                             f'{VERSION_QUANT})')
+        return
+    if 'max_error' in meta:
+        raise ValueError(f'{path}: a version-{VERSION_QUANT} (error-bounded) file with a max_error entry')
+
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+    if not (isinstance(q, dict) and is_int(q.get('exp')) and quant.E_MIN <= q['exp'] <= quant.E_MAX and
+            isinstance(q.get('dtype'), str) and q['dtype'] in _QUANT_DTYPES and
+            is_int(q.get('exceptions')) and q['exceptions'] >= 0):
+        raise ValueError(f'{path}: a version-{VERSION_QUANT} (error-bounded) file with a bad quant entry {q!r}')
+    if meta.get('sample_dtype') != 'float32':
+        raise ValueError(f'{path}: a version-{VERSION_QUANT} (error-bounded) file of {meta.get("sample_dtype")!r} '
+                         f'samples (float32 only)')
+
+
+def _quant(meta):
+    """``(exp, torch dtype, E)`` of an error-bounded file whose header ``_read_head`` accepted, else None."""
+    q = meta.get('quant')
+    return None if q is None else (int(q['exp']), _QUANT_DTYPES[q['dtype']], int(q['exceptions']))
 
 
 def _max_error(meta):
@@ -277,7 +317,7 @@ def _read_head(f, path):
     if len(head) < _HEAD.size:
         raise ValueError(f'{path}: not a kompressor_amd file (too short)')
     magic, version, _, mlen = _HEAD.unpack(head)
-    if magic != MAGIC or version not in (1, 2, VERSION, VERSION_NEAR) or mlen > (1 << 26):
+    if magic != MAGIC or version not in (1, 2, VERSION, VERSION_NEAR, VERSION_QUANT) or mlen > (1 << 26):
         raise ValueError(f'{path}: not a kompressor_amd file (magic {magic!r}, version {version})')
     try:
         meta = json.loads(f.read(mlen).decode())
@@ -286,6 +326,7 @@ def _read_head(f, path):
         raise ValueError(f'{path}: corrupt metadata ({e})') from None
     _check_sample_dtype(meta, path)
     _check_max_error(meta, version, path)
+    _check_quant(meta, version, path)
     if version == 1 and meta.get('method') != 'planes':
         # version-1 'rice' payloads were the per-array KMPR format, replaced by the v2 bundle;
         # version-1 'planes' payloads are unchanged and still read
@@ -399,30 +440,10 @@ def _auto_levels(shape, ndim, max_levels=4):
     return max(levels, 1)
 
 
-def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0):
-    """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
-    :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int8 / int16
-    modular on the sign-mapped samples, int32 raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
-    reference's single-level ``encode`` (volume/encode_decode.py:30-56) applied to the previous
-    level's lowres, so only the coarsest lowres is stored raw -- entropy-code every array and write
-    ``path``.  Returns ``{'bytes', 'raw_bytes', 'ratio', 'bits_per_sample', 'levels'}``.
-    ``tile_crc=True`` (``method='rice'``) appends one CRC-32 per tile of 16384 samples, computed on the
-    device right after the encode, so :func:`read_region` verifies exactly the tiles it reads.
-    ``max_error = d > 0`` (uint8 / uint16 / int8 / int16 samples): near-lossless -- the closed loop of
-    ``near.encode_pyramid``, every restored sample within ``d`` of the original, which is checked on
-    the device before anything is written (a failed check raises and writes nothing); the file is
-    version 4 and the result also holds ``'max_error'`` and the measured ``'max_abs_error'``."""
-    near.check_max_error(near._input_dtype(highres), max_error)  # before the device is touched
-    t0 = time.perf_counter()
-    packing._check_method(method)
-    _check_tile_crc_method(tile_crc, method)
-    ndim, padding = predictor.ndim, predictor.padding
-    h, _ = dev.to_device(highres)
-    if max_error:
-        return _compress_near(path, h, predictor, levels, method, tile_crc, int(max_error), t0)
-    sample = _NP_NAME[h.dtype]
-    if h.dtype == torch.float32:
-        h = h.view(torch.uint32)
+def _lossless_levels(h, predictor, levels):
+    """The lossless pyramid of the device tensor ``h`` under its dtype's natural coder: ``(coarsest
+    lowres, every level's maps finest first, the metadata's level entries, levels)``."""
+    ndim = predictor.ndim
     coder = _nd.NATURAL_CODER.get(h.dtype)
     if coder is None:
         raise TypeError(f'no lossless coder for {h.dtype}')
@@ -437,6 +458,48 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
         arrays.extend(maps)
         meta_levels.append({'highres_shape': list(x.shape), 'dims': [int(d) for d in dims]})
         x = lowres
+    return x, arrays, meta_levels, levels
+
+
+def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None):
+    """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
+    :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int8 / int16
+    modular on the sign-mapped samples, int32 raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
+    reference's single-level ``encode`` (volume/encode_decode.py:30-56) applied to the previous
+    level's lowres, so only the coarsest lowres is stored raw -- entropy-code every array and write
+    ``path``.  Returns ``{'bytes', 'raw_bytes', 'ratio', 'bits_per_sample', 'levels'}``.
+    ``tile_crc=True`` (``method='rice'``) appends one CRC-32 per tile of 16384 samples, computed on the
+    device right after the encode, so :func:`read_region` verifies exactly the tiles it reads.
+    ``max_error = d > 0`` (uint8 / uint16 / int8 / int16 samples): near-lossless -- the closed loop of
+    ``near.encode_pyramid``, every restored sample within ``d`` of the original, which is checked on
+    the device before anything is written (a failed check raises and writes nothing); the file is
+    version 4 and the result also holds ``'max_error'`` and the measured ``'max_abs_error'``.
+    ``abs_error`` (float32 samples; not with ``max_error``): error-bounded -- ``quant.quantise`` under the
+    bound, then the lossless pyramid of the int16 / int32 array; every restored value is within
+    ``quant.effective(abs_error)`` of the original and the values that cannot be quantised (not finite,
+    out of the integer range) come back bit for bit.  The bound is checked on the device before
+    anything is written; the file is version 5 and the result also holds ``'abs_error'`` (the effective
+    bound), ``'abs_error_asked'``, ``'max_abs_error'``, ``'exceptions'`` and ``'quant_dtype'``."""
+    exp = None
+    if abs_error is not None:  # before the device is touched
+        exp = quant.exponent(abs_error)
+        if max_error:
+            raise ValueError('abs_error (float32 samples) and max_error (8- / 16-bit integer samples) exclude each other')
+        quant._require_f32(highres, 'compress(abs_error=...)')
+    near.check_max_error(near._input_dtype(highres), max_error)  # before the device is touched
+    t0 = time.perf_counter()
+    packing._check_method(method)
+    _check_tile_crc_method(tile_crc, method)
+    ndim, padding = predictor.ndim, predictor.padding
+    h, _ = dev.to_device(highres)
+    if max_error:
+        return _compress_near(path, h, predictor, levels, method, tile_crc, int(max_error), t0)
+    if exp is not None:
+        return _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0)
+    sample = _NP_NAME[h.dtype]
+    if h.dtype == torch.float32:
+        h = h.view(torch.uint32)
+    x, arrays, meta_levels, levels = _lossless_levels(h, predictor, levels)
     meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'method': method,
             'sample_dtype': sample, 'levels': meta_levels, 'lowres_shape': list(x.shape),
             'predictor': _predictor_meta(predictor, padding, ndim, x.dtype)}
@@ -474,6 +537,60 @@ def _compress_near(path, h, predictor, levels, method, tile_crc, max_error, t0):
             'levels': levels, 'max_error': max_error, 'max_abs_error': worst}
 
 
+def _quant_max_error(h, n, exp, exceptions):
+    """``max |restore - h|`` over the non-exceptions, in float64, as a Python float: the dequantising
+    launch and the difference run slab by slab, so the temporaries stay bounded; one read-back."""
+    hf, nf = h.reshape(-1), n.reshape(-1)
+    worst = torch.zeros((), dtype=torch.float64, device='cuda')
+    idx = None if exceptions is None else exceptions[0]
+    for s in range(0, hf.numel(), _QUANT_SLAB):
+        e = min(s + _QUANT_SLAB, hf.numel())
+        d = (quant.d_code(_lib_decode, n.dtype, exp, nf[s:e]).double() - hf[s:e].double()).abs_()
+        if idx is not None:
+            i0, i1 = torch.searchsorted(idx, torch.tensor([s, e], device='cuda')).tolist()
+            d[idx[i0:i1] - s] = 0.0
+        worst = torch.maximum(worst, d.max())
+    return float(worst.item())
+
+
+def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0):
+    """:func:`compress` with ``abs_error``: the quantiser, the lossless pyramid of its integers, the
+    bound's check, the version-5 file."""
+    ndim, padding = predictor.ndim, predictor.padding
+    n, exc = quant.d_quantise(h, exp)
+    x, arrays, meta_levels, levels = _lossless_levels(n, predictor, levels)
+    E = 0 if exc is None else int(exc[0].numel())
+    eps = quant.effective(abs_error)
+    worst = _quant_max_error(h, n, exp, exc)
+    if not worst <= eps:
+        raise RuntimeError(f'error-bounded encode broke its bound: max |restored - highres| = {worst} > {eps} '
+                           f'(abs_error = {abs_error}); nothing written to {path}')
+    if E:  # the exceptions ride behind the maps: gap words (low, high), then the bits
+        arrays = [*arrays, *quant.d_gaps(exc[0]), exc[1]]
+    meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'method': method,
+            'sample_dtype': 'float32', 'levels': meta_levels, 'lowres_shape': list(x.shape),
+            'predictor': _predictor_meta(predictor, padding, ndim, x.dtype),
+            'quant': {'exp': exp, 'dtype': _NP_NAME[n.dtype], 'exceptions': E}}
+    blob, total, crc, table = _bundle(x, arrays, (), method, tile_crc)
+    nbytes = _write(path, meta, blob, total, crc, t0, table, VERSION_QUANT)
+    raw = h.numel() * h.element_size()
+    return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
+            'levels': levels, 'abs_error': eps, 'abs_error_asked': float(abs_error), 'max_abs_error': worst,
+            'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype]}
+
+
+def _quant_exceptions(path, arrays, E, numel):
+    """``(indices, bits)`` from a version-5 bundle's last three arrays, checked (E entries each, uint32,
+    every index inside the array) before anything is scattered by them."""
+    lo, hi, bits = arrays
+    if any(a.dtype != torch.uint32 or tuple(a.shape) != (E,) for a in arrays):
+        raise ValueError(f'{path}: the exception arrays do not match the metadata ({E} exceptions)')
+    idx = quant.d_indices(lo, hi)
+    if int(idx.min().item()) < 0 or int(idx.max().item()) >= numel:
+        raise ValueError(f'{path}: an exception index lies outside the array (corrupt file)')
+    return idx, bits
+
+
 def _decode_predictor(path, meta, predictor, dtype):
     """The predictor a file decodes with -- the one passed, or the file's own -- checked against the
     file's padding and a LinearPredictor's arithmetic (``dtype``: the coded samples' torch dtype).
@@ -505,6 +622,14 @@ def decompress(path, predictor=None, as_numpy=True):
     _check_crc(path, meta, crc, blob)
     t1 = time.perf_counter()
     lowres, (arrays, bundle_dims) = packing.unpack_encoded(blob)
+    q, extra = _quant(meta), None
+    if q is not None:
+        if lowres.dtype != q[1]:
+            raise ValueError(f'{path}: the bundle holds {lowres.dtype} samples, the metadata says {q[1]}')
+        if q[2]:  # the three exception arrays behind the maps
+            if len(arrays) < 3:
+                raise ValueError(f'{path}: the exception arrays are missing from the bundle')
+            arrays, extra = arrays[:-3], arrays[-3:]
     pred = _decode_predictor(path, meta, predictor, lowres.dtype)
     ndim, padding = meta['ndim'], meta['padding']
     nmaps = _nd.NMAPS[ndim]
@@ -524,7 +649,9 @@ def decompress(path, predictor=None, as_numpy=True):
         else:
             out = _nd.decode(pred, dec_fn, x, (maps, dims), padding, ndim)
         x = out
-    if meta.get('sample_dtype') == 'float32':
+    if q is not None:  # one dequantising launch, then the exceptions' bits
+        x = quant.d_restore(x, q[0], None if extra is None else _quant_exceptions(path, extra, q[2], x.numel()))
+    elif meta.get('sample_dtype') == 'float32':
         x = x.view(torch.float32)
     torch.cuda.current_stream().synchronize()
     t2 = time.perf_counter()
@@ -582,6 +709,9 @@ def info(path):
                'file_bytes': int(size), 'bundle_bytes': int(n)}
         if _max_error(meta):  # only a near-lossless file reports a bound
             out['max_error'] = _max_error(meta)
+        if _quant(meta) is not None:  # only an error-bounded file reports its bound
+            exp, qdt, E = _quant(meta)
+            out.update(abs_error=2.0 ** (exp - 1), quant_dtype=_NP_NAME[qdt], exceptions=E)
         trailer = _tile_crc_trailer(meta, n, size - (_HEAD.size + mlen), path)
         if trailer is not None:  # only a file that has a table reports one
             out['tile_crc'] = trailer[1]
@@ -594,7 +724,16 @@ def _meta_tile_counts(meta):
     """The tile count of every bundle array, in bundle order (the coarsest lowres, then each level's
     maps, finest level first), from the metadata's shapes alone."""
     shapes = _meta_shapes(meta)
-    return [_tiles(dev.prod(shapes[-1][1]))] + [_tiles(dev.prod(m)) for _, _, maps, _ in shapes for m in maps]
+    return [_tiles(dev.prod(shapes[-1][1]))] + [_tiles(dev.prod(m)) for _, _, maps, _ in shapes for m in maps] + \
+        [_tiles(n) for n in _exception_arrays(meta)]
+
+
+def _exception_arrays(meta):
+    """The lengths of the arrays behind the maps: three of E entries in an error-bounded file that has
+    exceptions, none in any other file."""
+    q = meta.get('quant')
+    E = int(q['exceptions']) if isinstance(q, dict) else 0
+    return [E] * 3 if E > 0 else []
 
 
 def _tile_begins(counts):
@@ -722,7 +861,8 @@ def plan_region(meta, planes=None, batch=None, rows=None, cols=None, level=0):
     ``k``, which have no ranges), the offsets ``local_at`` and ``local_row_at`` the selection starts at
     there and ``ranges`` [(first sample, end sample, destination sample)] -- one per array, one per
     batch item when only the first axis is restricted, one per batch item and plane (a row run) where
-    rows are cropped --, 'tiles_decoded': tiles the launches decode, counted per range,
+    rows are cropped; an error-bounded file with exceptions has three more entries behind the maps, its
+    exception arrays, each read whole --, 'tiles_decoded': tiles the launches decode, counted per range,
     'tiles_total': tiles in the file}``."""
     ndim, p = int(meta['ndim']), int(meta['padding'])
     shapes = _meta_shapes(meta)
@@ -801,6 +941,9 @@ def plan_region(meta, planes=None, batch=None, rows=None, cols=None, level=0):
     arrays = [entry(lo_shape, lowres_axes[:ncrop], [e - s for s, e in lowres_axes[:ncrop]], [0] * ncrop)] + \
         skipped + map_entries
     assert len(arrays) == 1 + nmaps * nlev
+    # an error-bounded file's exception arrays (gap words, bits) are read whole, whatever the selection
+    arrays += [{'shape': (E,), 'sel': (0, E), 'local_shape': (E,), 'local_at': 0, 'sel_rows': (0, E), 'local_row_at': 0,
+                'ranges': [(0, E, 0)]} for E in _exception_arrays(meta)]
     for i, e in enumerate(arrays):
         e['index'] = i
     return {'batch': (b0, b1), 'planes': box[0], 'rows': box[ndim - 2], 'cols': box[ndim - 1], 'box': tuple(box),
@@ -900,6 +1043,35 @@ def _region_windows(fd, path, base, nbytes, rplan, plan, crc_table=None):
     return buf, used, jobs, payload_bytes, crc_offs
 
 
+def _region_restore(meta, plan, x, extra):
+    """The float32 box of an error-bounded file from its integer box ``x`` (contiguous): one
+    dequantising launch, then the bits of the exceptions that fall in it -- at level ``k`` those whose
+    spatial coordinates are all multiples of ``2**k``.  ``extra``: the gap words and the bits, or None.
+    Every index is masked to the box before it addresses anything, so damaged arrays cannot write
+    outside the result (the caller's tile checks report them)."""
+    exp, _, _ = _quant(meta)
+    out = quant.d_restore(x, exp, None)
+    if extra is None:
+        return out
+    ndim, k = int(meta['ndim']), plan['level']
+    shape0 = _meta_shapes(meta)[0][0]
+    idx, bits = quant.d_indices(extra[0], extra[1]), extra[2]
+    spans = [plan['batch'], *plan['box'], *[(0, s) for s in shape0[1 + ndim:]]]
+    keep = (idx >= 0) & (idx < dev.prod(shape0))
+    flat, rem, stride = torch.zeros_like(idx), idx, 1
+    for a in reversed(range(len(shape0))):
+        c, rem = rem % shape0[a], rem // shape0[a]
+        if 1 <= a <= ndim:
+            keep &= (c & ((1 << k) - 1)) == 0
+            c = c >> k
+        lo, hi = spans[a]
+        keep &= (c >= lo) & (c < hi)
+        flat += (c - lo) * stride
+        stride *= hi - lo
+    out.reshape(-1).view(torch.int32)[flat[keep]] = bits.view(torch.int32)[keep]
+    return out
+
+
 def level_shapes(path):
     """The shape of every pyramid level of a file, from its header and metadata alone (no payload
     read, no GPU): ``[level 0 (the array decompress returns), level 1, ..., level L]`` for a file of
@@ -996,6 +1168,11 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
         if [tuple(s) for s in rplan['shapes']] != [ar['shape'] for ar in arrays]:
             raise ValueError(f'{path}: the bundle\'s arrays do not match the metadata\'s levels')
         dtype = dev.CODE_TO_TORCH[rplan['codes'][0]]
+        q = _quant(meta)
+        if q is not None and dtype != q[1]:
+            raise ValueError(f'{path}: the bundle holds {dtype} samples, the metadata says {q[1]}')
+        if q is not None and q[2] and any(dev.CODE_TO_TORCH[c] != torch.uint32 for c in rplan['codes'][-3:]):
+            raise ValueError(f'{path}: the exception arrays of the bundle are not uint32')
         pred = _decode_predictor(path, meta, predictor, dtype)
         buf, used, jobs, payload_bytes, crc_offs = _region_windows(fd, path, base, nbytes, rplan, plan, trailer)
     t1 = time.perf_counter()
@@ -1052,7 +1229,9 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
             x = x.contiguous()
     if not plan['levels']:  # the stored coarsest lowres itself
         x = x[(slice(None), *[slice(s - lo, e - lo) for (s, e), (lo, _) in zip(plan['box'], plan['lowres_axes'])])]
-    if meta.get('sample_dtype') == 'float32':
+    if q is not None:
+        x = _region_restore(meta, plan, x.contiguous(), local[-3:] if q[2] else None)
+    elif meta.get('sample_dtype') == 'float32':
         x = x.contiguous().view(torch.float32)
     nbad, ncrc = bad.tolist()  # the synchronisation
     if nbad:

@@ -330,6 +330,8 @@ inline NearQ make_nearq(int32_t delta) { return NearQ{delta, 2 * delta + 1, make
 inline int coder_code(int32_t coder) { return coder & 0xff; }
 inline int32_t coder_max_error(int32_t coder) { return (int32_t)((uint32_t)coder >> 8); }
 inline bool is_near_code(int code) { return code == KMP_CODER_NEAR_U8 || code == KMP_CODER_NEAR_U16; }
+// the float32 quantisers are kmp_code's alone: check_coder_arg refuses them everywhere else
+inline bool is_quant_code(int code) { return code == KMP_CODER_QUANT_I16 || code == KMP_CODER_QUANT_I32; }
 // KMP_OK for a well-formed ``coder`` argument whose sample width (bytes) is ``width``: a lossless
 // code carries no max_error; a near code's width is the samples' (1 / 2; none for 32-bit samples:
 // KMP_ERR_UNSUPPORTED) and 1 <= max_error <= 2^(W-1) - 1
@@ -377,6 +379,7 @@ __device__ __forceinline__ typename coder_out<CODER>::type coder_dec(const NearQ
 
 // 16-byte vectors: aligned, and any-alignment (gfx950 serves unaligned dwordx4 global accesses;
 // rows of odd length are only element-aligned)
+typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
 

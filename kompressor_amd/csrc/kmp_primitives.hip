@@ -258,6 +258,68 @@ __global__ void __launch_bounds__(kThreads) code_near_kernel(const TP* __restric
   }
 }
 
+// Error-bounded float32 quantisers (KMP_CODER_QUANT_I16 / _I32).  The step is a power
+// of two, so the float64 products are exact and the one rounding is the final conversion to float32:
+// the same bits as tests/quant_spec.py on any device.  An exception (not finite, out of the integer
+// type's range, or further than eps from its restored value) is written as the type's minimum.
+struct QuantP {
+  double inv, step, eps;  // 2^-e, 2^e, 2^(e-1)
+};
+
+template <typename TN>
+__device__ __forceinline__ TN quant_one(float x, const QuantP& q) {
+  constexpr double QMAX = (double)std::numeric_limits<TN>::max();
+  const double xd = (double)x;
+  const double n = __builtin_rint(xd * q.inv);  // NaN and infinities stay what they are
+  const float r = (float)(n * q.step);
+  // every comparison is false for a NaN; an infinite x gives an infinite n
+  const bool ok = __builtin_fabs(n) <= QMAX && __builtin_fabsf(r) <= std::numeric_limits<float>::max() &&
+                  __builtin_fabs((double)r - xd) <= q.eps;
+  return ok ? (TN)(int32_t)n : std::numeric_limits<TN>::min();
+}
+
+template <typename TN>
+__device__ __forceinline__ float dequant_one(TN n, const QuantP& q) {
+  return (float)((double)n * q.step);
+}
+
+// element form: any alignment, any count
+template <int DIR, typename TN>
+__global__ void __launch_bounds__(kThreads) quant_kernel(const void* __restrict__ x, int64_t n, void* __restrict__ out,
+                                                       QuantP q) {
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (DIR == KMP_ENCODE) ((TN*)out)[t] = quant_one<TN>(((const float*)x)[t], q);
+    else ((float*)out)[t] = dequant_one<TN>(((const TN*)x)[t], q);
+  }
+}
+
+// vector form: one item = four elements, a 16-byte access on the float32 side and an 8- (int16) or
+// 16-byte (int32) one on the integer side, both aligned to their size; ``n4`` items
+template <int DIR, typename TN>
+__global__ void __launch_bounds__(kThreads) quant_vec_kernel(const void* __restrict__ x, int64_t n4,
+                                                           void* __restrict__ out, QuantP q) {
+  using NV = typename std::conditional<sizeof(TN) == 2, u32x2v, u32x4v>::type;  // four TN
+  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < n4; t += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (DIR == KMP_ENCODE) {
+      const u32x4v xv = __builtin_nontemporal_load((const u32x4v*)x + t);
+      const float* xx = (const float*)&xv;
+      NV ov;
+      TN* oo = (TN*)&ov;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) oo[i] = quant_one<TN>(xx[i], q);
+      __builtin_nontemporal_store(ov, (NV*)out + t);
+    } else {
+      const NV xv = __builtin_nontemporal_load((const NV*)x + t);
+      const TN* xx = (const TN*)&xv;
+      u32x4v ov;
+      float* oo = (float*)&ov;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) oo[i] = dequant_one<TN>(xx[i], q);
+      __builtin_nontemporal_store(ov, (u32x4v*)out + t);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Box copy with conversion (slicing / .at[box].set of the chunk driver)
 // ------------------------------------------------------------------------------------------
@@ -653,6 +715,35 @@ int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* p
              int64_t n, void* out, kmp_stream_t stream) {
   KMP_REQUIRE(direction == KMP_ENCODE || direction == KMP_DECODE, "bad direction");
   KMP_REQUIRE(n >= 0, "negative count");
+  if (coder >= 0 && is_quant_code(coder_code(coder))) {
+    // float32 <-> int16 / int32 on a power-of-two step: no prediction, so none may be passed
+    const int code = coder_code(coder);
+    const int32_t field = coder >> 8;  // exponent + 127
+    const int ndt = code == KMP_CODER_QUANT_I16 ? KMP_I16 : KMP_I32;
+    KMP_REQUIRE(!pred, "the quantising coders take no prediction (pred must be NULL)");
+    KMP_REQUIRE(field >= 1 && field <= 254, "quantiser exponent outside [-126, 127]");
+    KMP_REQUIRE(x_dtype == (direction == KMP_ENCODE ? (int)KMP_F32 : ndt),
+                "quantising coders: float32 in (encode), the code's int16 / int32 in (decode)");
+    if (n == 0) return KMP_OK;
+    KMP_REQUIRE(x && out, "null pointer");
+    const int e = field - 127;
+    const QuantP q{std::ldexp(1.0, -e), std::ldexp(1.0, e), std::ldexp(1.0, e - 1)};
+    hipStream_t s = (hipStream_t)stream;
+    auto go = [&](auto dir_c, auto ntag) {
+      constexpr int DIR = decltype(dir_c)::value;
+      using TN = decltype(ntag);
+      // the integer side of a vector item is 4 * sizeof(TN) bytes, the float32 side 16
+      const uintptr_t fa = (uintptr_t)(DIR == KMP_ENCODE ? x : out), na = (uintptr_t)(DIR == KMP_ENCODE ? out : x);
+      if ((fa & 15) == 0 && (na & (4 * sizeof(TN) - 1)) == 0 && n % 4 == 0)
+        quant_vec_kernel<DIR, TN><<<grid_for(n / 4), kThreads, 0, s>>>(x, n / 4, out, q);
+      else
+        quant_kernel<DIR, TN><<<grid_for(n), kThreads, 0, s>>>(x, n, out, q);
+      return check_launch("code");
+    };
+    auto with_t = [&](auto dir_c) { return ndt == KMP_I16 ? go(dir_c, int16_t{}) : go(dir_c, int32_t{}); };
+    return direction == KMP_ENCODE ? with_t(std::integral_constant<int, KMP_ENCODE>{})
+                                   : with_t(std::integral_constant<int, KMP_DECODE>{});
+  }
   if (n == 0) return KMP_OK;
   KMP_REQUIRE(pred && x && out, "null pointer");
   hipStream_t s = (hipStream_t)stream;

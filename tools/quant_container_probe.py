@@ -1,0 +1,58 @@
+"""compress / decompress of a 512^3 float32 smooth-plus-noise field at abs_error None, 1e-1, 1e-2, 1e-3:
+file size, bits per sample and the last_timing splits; three timed rounds, the bounds alternated within
+each.  ``--nan`` turns about 10 % of the volume (a slab of planes) into NaN: the cost of the exception
+path.  ``--lossless-only`` runs the ``None`` row alone and passes no keyword, so the same script
+measures a build from before error-bounded coding."""
+import json, os, sys, tempfile
+import numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import kompressor_amd as kom
+from kompressor_amd import container
+
+rng = np.random.default_rng(0)
+n = 512
+ax = np.linspace(0, 1, n, dtype=np.float32)
+f = np.zeros((n, n, n), np.float32)
+for _ in range(4):
+    k = rng.uniform(0.5, 2.5, 3).astype(np.float32); ph = np.float32(rng.uniform(0, 2 * np.pi))
+    f += np.sin(2 * np.pi * (k[0] * ax[:, None, None] + k[1] * ax[None, :, None] + k[2] * ax[None, None, :]) + ph)
+f /= np.abs(f).max()
+x = (f + rng.standard_normal((n, n, n), dtype=np.float32) / 15).astype(np.float32)  # noise 1/15 of the amplitude
+if '--nan' in sys.argv:
+    x[200:251] = np.nan
+x = x.reshape(1, n, n, n, 1)
+xt = torch.from_numpy(x).cuda()
+pred = kom.MeanPredictor(0, 3)
+d = tempfile.mkdtemp(dir='/dev/shm' if os.path.isdir('/dev/shm') else None)
+bounds = (None,) if '--lossless-only' in sys.argv else (None, 1e-1, 1e-2, 1e-3)
+out = {}
+for rnd in range(4):
+    for a in bounds:
+        path = os.path.join(d, 'v.kmp')
+        res = container.compress(path, xt, pred, levels=3, **({} if a is None else {'abs_error': a}))
+        tc = dict(container.last_timing)
+        torch.cuda.synchronize()
+        y = container.decompress(path, as_numpy=False)
+        td = dict(container.last_timing)
+        if a is None:
+            assert torch.equal(y.view(torch.int32), xt.view(torch.int32))
+        else:
+            err = (y.double() - xt.double()).abs()
+            assert float(err[torch.isfinite(xt)].max().item()) == res['max_abs_error'] <= res['abs_error']
+            assert torch.equal(y.view(torch.int32)[~torch.isfinite(xt)], xt.view(torch.int32)[~torch.isfinite(xt)])
+            del err
+        del y
+        if rnd:  # round 0 warms up
+            out.setdefault(a, []).append((res, tc, td))
+        os.remove(path)
+for a, runs in out.items():
+    med = lambda xs: float(np.median(xs))
+    res = runs[0][0]
+    line = {'abs_error': a, 'nan_slab': '--nan' in sys.argv, 'bytes': res['bytes'],
+            'bits_per_sample': round(res['bits_per_sample'], 4),
+            **{k: res[k] for k in ('abs_error', 'max_abs_error', 'exceptions', 'quant_dtype') if k in res and a is not None},
+            'abs_error_asked': a,
+            'compress_ms': {k: [round(1e3 * f([r[1][k] for r in runs]), 2) for f in (med, min, max)] for k in runs[0][1]},
+            'decompress_ms': {k: [round(1e3 * f([r[2][k] for r in runs]), 2) for f in (med, min, max)]
+                              for k in runs[0][2] if isinstance(runs[0][2][k], float)}}
+    print(json.dumps(line), flush=True)
