@@ -66,10 +66,24 @@ typedef enum {
      writes the float32 r of every element.  They take no prediction: ``pred`` must be NULL and
      ``pred_dtype`` is not read.  A non-NULL pred, an exponent field of 0 or >= 255, an x_dtype that
      does not fit, or these codes on any other entry point: KMP_ERR_ARG. */
-  KMP_CODER_QUANT_I16 = 6, KMP_CODER_QUANT_I32 = 7
+  KMP_CODER_QUANT_I16 = 6, KMP_CODER_QUANT_I32 = 7,
+  /* Relative-error float32 quantisers (kmp_code alone).  They keep the top m mantissa
+     bits, 0 <= m <= 22, and the ``coder`` argument carries KMP_CODER_PREC(code, m).  With t = 23 - m,
+     QMAX as above, u the float32's bits, s = u >> 31 and a = u & 0x7fffffff, in 32-bit unsigned arithmetic:
+       k = (a + 2^(t-1) - 1 + ((a >> t) & 1)) >> t                (round to nearest, ties to even)
+       x is an exception iff a >= 0x7f800000, (k << t) >= 0x7f800000 or k > QMAX;  n = s ? -k : k.
+     ENCODE (x_dtype = KMP_F32) writes n as int16 / int32, an exception as the type's minimum (no legal
+     n takes it: |n| <= 255 2^m - 1); DECODE (x_dtype = KMP_I16 / KMP_I32, matching the code) writes for
+     every element the float32 of bits ((|n| << t) & 0x7fffffff) | (n < 0 ? 0x80000000 : 0), |n| as
+     uint32.  Every non-exception restores within 2^-(m+1) max(|x|, 2^-126) of x.  ``pred`` must be
+     NULL and ``pred_dtype`` is not read.  A non-NULL pred, a field (m + 1) outside [1, 23] -- a bare
+     8 or 9 included --, an x_dtype that does not fit, or these codes on any other entry point:
+     KMP_ERR_ARG. */
+  KMP_CODER_PREC_I16 = 8, KMP_CODER_PREC_I32 = 9
 } kmp_coder;
 #define KMP_CODER_NEAR(code, max_error) ((code) | ((max_error) << 8))
 #define KMP_CODER_QUANT(code, exp) ((code) | (((exp) + 127) << 8))
+#define KMP_CODER_PREC(code, m) ((code) | (((m) + 1) << 8))
 typedef enum { KMP_ENCODE = 0, KMP_DECODE = 1 } kmp_direction;
 
 typedef enum {
@@ -277,8 +291,8 @@ int kmp_tiles(int32_t nsp, int32_t dtype, int32_t direction, const void* src, co
    which says whether they are signed -- and ``pred_dtype`` is that dtype or KMP_F32 (truncated, then
    clamped to the sample type's range).  The output is the unsigned map (encode) or the samples'
    bit patterns (decode).
-   Quantisers (KMP_CODER_QUANT, see kmp_coder): ``pred`` is NULL; float32 -> int16 / int32 (ENCODE),
-   int16 / int32 -> float32 (DECODE). */
+   Quantisers (KMP_CODER_QUANT and KMP_CODER_PREC, see kmp_coder): ``pred`` is NULL; float32 ->
+   int16 / int32 (ENCODE), int16 / int32 -> float32 (DECODE). */
 int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* pred, int32_t x_dtype,
              const void* x, int64_t n, void* out, kmp_stream_t stream);
 

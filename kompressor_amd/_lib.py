@@ -48,6 +48,15 @@ def coder_quant(code, exp):
     return int(code) | ((int(exp) + 127) << 8)
 
 
+# relative-error float32 quantisers (kmp_code alone): the argument carries coder_prec(code, mantissa bits)
+CODER_PREC_I16, CODER_PREC_I32 = 8, 9
+
+
+def coder_prec(code, m):
+    """KMP_CODER_PREC(code, m): the quantiser ``code`` keeping the top ``m`` mantissa bits."""
+    return int(code) | ((int(m) + 1) << 8)
+
+
 def coder_code(coder):
     return int(coder) & 0xff
 

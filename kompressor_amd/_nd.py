@@ -38,7 +38,8 @@ class _CoderDtype(dict):
 
 NEAR_WIDTH = {_lib.CODER_NEAR_U8: 1, _lib.CODER_NEAR_U16: 2}  # the near coders' sample width, bytes
 # the float32 quantisers' integer dtype (an encode's output, a decode's input; kom.quant)
-QUANT_DTYPE = {_lib.CODER_QUANT_I16: torch.int16, _lib.CODER_QUANT_I32: torch.int32}
+QUANT_DTYPE = {_lib.CODER_QUANT_I16: torch.int16, _lib.CODER_QUANT_I32: torch.int32,
+               _lib.CODER_PREC_I16: torch.int16, _lib.CODER_PREC_I32: torch.int32}
 CODER_DTYPE = _CoderDtype({_lib.CODER_RAW: torch.int32, _lib.CODER_U8: torch.uint8, _lib.CODER_U16: torch.uint16,
                            _lib.CODER_U32: torch.uint32, _lib.CODER_NEAR_U8: torch.uint8,
                            _lib.CODER_NEAR_U16: torch.uint16, **QUANT_DTYPE})

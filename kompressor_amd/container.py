@@ -24,7 +24,8 @@ start; ``packing.tile_crcs``): ``read_region`` verifies the tiles it touches aga
 and a failing ``decompress`` name the damaged ones.  ``bundle_bytes`` and ``crc32`` cover the bundle
 alone either way, and a reader that does not know the key reads the file as before.
 Version 4 is a near-lossless file (``'max_error'``), version 5 an error-bounded float32 file
-(``'quant'``, and its exception arrays behind the maps); see ``VERSION_NEAR`` / ``VERSION_QUANT`` below.
+(``'quant'``, and its exception arrays behind the maps), version 6 a relative-error float32 file
+(``'prec'``); see ``VERSION_NEAR`` / ``VERSION_QUANT`` / ``VERSION_PREC`` below.
 
 The host side of the file path (round 4): the bundle's CRC-32 (zlib's, the value the file stores)
 is computed on the device (``kmp_crc32``) -- over the bundle the encode just wrote, its length read
@@ -64,7 +65,11 @@ VERSION_NEAR = 4
 # and the high words of the gaps between consecutive sorted flat indices (the first gap is the first
 # index), and the bits.  Older builds refuse version 5.
 VERSION_QUANT = 5
-_QUANT_DTYPES = {'int16': torch.int16, 'int32': torch.int32}
+# 6: a relative-error float32 file: as version 5, but the integers are those of
+# ``quant.quantise_rel`` and the metadata's 'prec' = {'bits', 'dtype', 'exceptions': E} records the
+# mantissa bits kept in place of 'quant'.  The exception arrays are version 5's.  Older builds refuse it.
+VERSION_PREC = 6
+_QUANT_DTYPES ={'int16': torch.int16, 'int32': torch.int32}
 _QUANT_SLAB = 1 << 24  # elements per slab of the bound's check
 _HEAD = struct.Struct('<4sHHQ')
 _NP_NAME = {torch.uint8: 'uint8', torch.uint16: 'uint16', torch.int32: 'int32', torch.uint32: 'uint32',
@@ -126,10 +131,38 @@ def _check_quant(meta, version, path):
                          f'samples (float32 only)')
 
 
+def _check_prec(meta, version, path):
+    """A version-6 file is float32, states a well-formed 'prec' and carries neither 'quant' nor
+    'max_error'; no other version has a 'prec'."""
+    p = meta.get('prec')
+    if version != VERSION_PREC:
+        if p is not None:
+            raise ValueError(f'{path}: a version-{version} file with a prec entry (relative-error files are version '
+                             f'{VERSION_PREC})')
+        return
+    for key in ('max_error', 'quant'):
+        if key in meta:
+            raise ValueError(f'{path}: a version-{VERSION_PREC} (relative-error) file with a {key} entry')
+
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+    if not (isinstance(p, dict) and is_int(p.get('bits')) and quant.M_MIN <= p['bits'] <= quant.M_MAX and
+            isinstance(p.get('dtype'), str) and p['dtype'] in _QUANT_DTYPES and
+            is_int(p.get('exceptions')) and p['exceptions'] >= 0):
+        raise ValueError(f'{path}: a version-{VERSION_PREC} (relative-error) file with a bad prec entry {p!r}')
+    if meta.get('sample_dtype') != 'float32':
+        raise ValueError(f'{path}: a version-{VERSION_PREC} (relative-error) file of {meta.get("sample_dtype")!r} '
+                         f'samples (float32 only)')
+
+
 def _quant(meta):
-    """``(exp, torch dtype, E)`` of an error-bounded file whose header ``_read_head`` accepted, else None."""
-    q = meta.get('quant')
-    return None if q is None else (int(q['exp']), _QUANT_DTYPES[q['dtype']], int(q['exceptions']))
+    """``(exp or kept mantissa bits, torch dtype, E, the restoring function)`` of an error-bounded
+    ('quant') or relative-error ('prec') file whose header ``_read_head`` accepted, else None."""
+    for key, param, d_restore in (('quant', 'exp', quant.d_restore), ('prec', 'bits', quant.d_restore_rel)):
+        q = meta.get(key)
+        if q is not None:
+            return int(q[param]), _QUANT_DTYPES[q['dtype']], int(q['exceptions']), d_restore
+    return None
 
 
 def _max_error(meta):
@@ -317,7 +350,7 @@ def _read_head(f, path):
     if len(head) < _HEAD.size:
         raise ValueError(f'{path}: not a kompressor_amd file (too short)')
     magic, version, _, mlen = _HEAD.unpack(head)
-    if magic != MAGIC or version not in (1, 2, VERSION, VERSION_NEAR, VERSION_QUANT) or mlen > (1 << 26):
+    if magic != MAGIC or version not in (1, 2, VERSION, VERSION_NEAR, VERSION_QUANT, VERSION_PREC) or mlen > (1 << 26):
         raise ValueError(f'{path}: not a kompressor_amd file (magic {magic!r}, version {version})')
     try:
         meta = json.loads(f.read(mlen).decode())
@@ -327,6 +360,7 @@ def _read_head(f, path):
     _check_sample_dtype(meta, path)
     _check_max_error(meta, version, path)
     _check_quant(meta, version, path)
+    _check_prec(meta, version, path)
     if version == 1 and meta.get('method') != 'planes':
         # version-1 'rice' payloads were the per-array KMPR format, replaced by the v2 bundle;
         # version-1 'planes' payloads are unchanged and still read
@@ -461,7 +495,8 @@ def _lossless_levels(h, predictor, levels):
     return x, arrays, meta_levels, levels
 
 
-def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None):
+def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None,
+             rel_error=None):
     """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
     :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int8 / int16
     modular on the sign-mapped samples, int32 raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
@@ -479,8 +514,19 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
     ``quant.effective(abs_error)`` of the original and the values that cannot be quantised (not finite,
     out of the integer range) come back bit for bit.  The bound is checked on the device before
     anything is written; the file is version 5 and the result also holds ``'abs_error'`` (the effective
-    bound), ``'abs_error_asked'``, ``'max_abs_error'``, ``'exceptions'`` and ``'quant_dtype'``."""
-    exp = None
+    bound), ``'abs_error_asked'``, ``'max_abs_error'``, ``'exceptions'`` and ``'quant_dtype'``.
+    ``rel_error`` (float32 samples; alone of the three bounds): pointwise relative -- ``quant.quantise_rel``,
+    then the same pyramid; every restored value ``r`` of a finite ``x`` has ``|r - x| <=
+    quant.effective_rel(rel_error) * max(|x|, 2**-126)``, what is not finite or rounds up to infinity
+    comes back bit for bit.  Checked on the device before anything is written; the file is version 6
+    and the result also holds ``'rel_error'`` (the effective bound), ``'rel_error_asked'``,
+    ``'max_rel_error'``, ``'exceptions'`` and ``'quant_dtype'``."""
+    exp = bits = None
+    if rel_error is not None:  # before the device is touched
+        bits = quant.mantissa_bits(rel_error)
+        if max_error or abs_error is not None:
+            raise ValueError('max_error, abs_error and rel_error exclude each other')
+        quant._require_f32(highres, 'compress(rel_error=...)')
     if abs_error is not None:  # before the device is touched
         exp = quant.exponent(abs_error)
         if max_error:
@@ -496,6 +542,8 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
         return _compress_near(path, h, predictor, levels, method, tile_crc, int(max_error), t0)
     if exp is not None:
         return _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0)
+    if bits is not None:
+        return _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0)
     sample = _NP_NAME[h.dtype]
     if h.dtype == torch.float32:
         h = h.view(torch.uint32)
@@ -579,6 +627,49 @@ def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp
             'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype]}
 
 
+def _prec_max_error(h, n, bits, exceptions):
+    """``max |restore - h| / max(|h|, 2^-126)`` over the non-exceptions, in float64, as a Python float:
+    slab by slab like :func:`_quant_max_error`, one read-back."""
+    hf, nf = h.reshape(-1), n.reshape(-1)
+    worst = torch.zeros((), dtype=torch.float64, device='cuda')
+    idx = None if exceptions is None else exceptions[0]
+    for s in range(0, hf.numel(), _QUANT_SLAB):
+        e = min(s + _QUANT_SLAB, hf.numel())
+        xd = hf[s:e].double()
+        d = (quant.d_code_rel(_lib_decode, n.dtype, bits, nf[s:e]).double() - xd).abs_() / xd.abs_().clamp_min_(2.0 ** -126)
+        if idx is not None:
+            i0, i1 = torch.searchsorted(idx, torch.tensor([s, e], device='cuda')).tolist()
+            d[idx[i0:i1] - s] = 0.0
+        worst = torch.maximum(worst, d.max())
+    return float(worst.item())
+
+
+def _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0):
+    """:func:`compress` with ``rel_error``: the mantissa quantiser, the lossless pyramid of its integers,
+    the guarantee's check, the version-6 file."""
+    ndim, padding = predictor.ndim, predictor.padding
+    n, exc = quant.d_quantise_rel(h, bits)
+    x, arrays, meta_levels, levels = _lossless_levels(n, predictor, levels)
+    E = 0 if exc is None else int(exc[0].numel())
+    eps = quant.effective_rel(rel_error)
+    worst = _prec_max_error(h, n, bits, exc)
+    if not worst <= eps:
+        raise RuntimeError(f'relative-error encode broke its bound: max |restored - highres| / max(|highres|, 2^-126) '
+                           f'= {worst} > {eps} (rel_error = {rel_error}); nothing written to {path}')
+    if E:  # the exceptions ride behind the maps: gap words (low, high), then the bits
+        arrays = [*arrays, *quant.d_gaps(exc[0]), exc[1]]
+    meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'method': method,
+            'sample_dtype': 'float32', 'levels': meta_levels, 'lowres_shape': list(x.shape),
+            'predictor': _predictor_meta(predictor, padding, ndim, x.dtype),
+            'prec': {'bits': bits, 'dtype': _NP_NAME[n.dtype], 'exceptions': E}}
+    blob, total, crc, table = _bundle(x, arrays, (), method, tile_crc)
+    nbytes = _write(path, meta, blob, total, crc, t0, table, VERSION_PREC)
+    raw = h.numel() * h.element_size()
+    return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
+            'levels': levels, 'rel_error': eps, 'rel_error_asked': float(rel_error), 'max_rel_error': worst,
+            'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype]}
+
+
 def _quant_exceptions(path, arrays, E, numel):
     """``(indices, bits)`` from a version-5 bundle's last three arrays, checked (E entries each, uint32,
     every index inside the array) before anything is scattered by them."""
@@ -650,7 +741,7 @@ def decompress(path, predictor=None, as_numpy=True):
             out = _nd.decode(pred, dec_fn, x, (maps, dims), padding, ndim)
         x = out
     if q is not None:  # one dequantising launch, then the exceptions' bits
-        x = quant.d_restore(x, q[0], None if extra is None else _quant_exceptions(path, extra, q[2], x.numel()))
+        x = q[3](x, q[0], None if extra is None else _quant_exceptions(path, extra, q[2], x.numel()))
     elif meta.get('sample_dtype') == 'float32':
         x = x.view(torch.float32)
     torch.cuda.current_stream().synchronize()
@@ -709,9 +800,10 @@ def info(path):
                'file_bytes': int(size), 'bundle_bytes': int(n)}
         if _max_error(meta):  # only a near-lossless file reports a bound
             out['max_error'] = _max_error(meta)
-        if _quant(meta) is not None:  # only an error-bounded file reports its bound
-            exp, qdt, E = _quant(meta)
-            out.update(abs_error=2.0 ** (exp - 1), quant_dtype=_NP_NAME[qdt], exceptions=E)
+        if _quant(meta) is not None:  # only an error-bounded or a relative-error file reports its bound
+            param, qdt, E, _ = _quant(meta)
+            out.update(quant_dtype=_NP_NAME[qdt], exceptions=E,
+                       **({'rel_error': 2.0 ** -(param + 1)} if 'prec' in meta else {'abs_error': 2.0 ** (param - 1)}))
         trailer = _tile_crc_trailer(meta, n, size - (_HEAD.size + mlen), path)
         if trailer is not None:  # only a file that has a table reports one
             out['tile_crc'] = trailer[1]
@@ -729,9 +821,9 @@ def _meta_tile_counts(meta):
 
 
 def _exception_arrays(meta):
-    """The lengths of the arrays behind the maps: three of E entries in an error-bounded file that has
-    exceptions, none in any other file."""
-    q = meta.get('quant')
+    """The lengths of the arrays behind the maps: three of E entries in an error-bounded or a
+    relative-error file that has exceptions, none in any other file."""
+    q = meta.get('quant') or meta.get('prec')
     E = int(q['exceptions']) if isinstance(q, dict) else 0
     return [E] * 3 if E > 0 else []
 
@@ -1049,8 +1141,8 @@ def _region_restore(meta, plan, x, extra):
     spatial coordinates are all multiples of ``2**k``.  ``extra``: the gap words and the bits, or None.
     Every index is masked to the box before it addresses anything, so damaged arrays cannot write
     outside the result (the caller's tile checks report them)."""
-    exp, _, _ = _quant(meta)
-    out = quant.d_restore(x, exp, None)
+    param, _, _, d_restore = _quant(meta)
+    out = d_restore(x, param, None)
     if extra is None:
         return out
     ndim, k = int(meta['ndim']), plan['level']

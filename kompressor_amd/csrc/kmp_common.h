@@ -332,6 +332,8 @@ inline int32_t coder_max_error(int32_t coder) { return (int32_t)((uint32_t)coder
 inline bool is_near_code(int code) { return code == KMP_CODER_NEAR_U8 || code == KMP_CODER_NEAR_U16; }
 // the float32 quantisers are kmp_code's alone: check_coder_arg refuses them everywhere else
 inline bool is_quant_code(int code) { return code == KMP_CODER_QUANT_I16 || code == KMP_CODER_QUANT_I32; }
+// so are the relative-error ones
+inline bool is_prec_code(int code) { return code == KMP_CODER_PREC_I16 || code == KMP_CODER_PREC_I32; }
 // KMP_OK for a well-formed ``coder`` argument whose sample width (bytes) is ``width``: a lossless
 // code carries no max_error; a near code's width is the samples' (1 / 2; none for 32-bit samples:
 // KMP_ERR_UNSUPPORTED) and 1 <= max_error <= 2^(W-1) - 1

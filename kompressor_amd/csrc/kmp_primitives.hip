@@ -320,6 +320,69 @@ __global__ void __launch_bounds__(kThreads) quant_vec_kernel(const void* __restr
   }
 }
 
+// Relative-error float32 quantisers (KMP_CODER_PREC_I16 / _I32): keep the top m mantissa
+// bits, rounded to nearest even, by shifts, adds and compares on the bit pattern -- ``t`` = 23 - m and
+// ``rnd`` = 2^(t-1) - 1 are kernel arguments.  The float32 side is loaded and stored as uint32 and no
+// floating-point instruction runs, so NaN payloads and subnormals pass whatever the mode registers
+// say: the same bits as tests/prec_spec.py on any device.  An exception (not finite, rounds up to
+// infinity, or out of the integer type's range) is written as the type's minimum.
+template <typename TN>
+__device__ __forceinline__ TN prec_one(uint32_t u, uint32_t t, uint32_t rnd) {
+  constexpr uint32_t QMAX = (uint32_t)std::numeric_limits<TN>::max();
+  const uint32_t a = u & 0x7fffffffu;
+  const uint32_t k = (a + rnd + ((a >> t) & 1u)) >> t;  // a + 2^22 < 2^32: no carry out
+  const bool exc = a >= 0x7f800000u || (k << t) >= 0x7f800000u || k > QMAX;
+  const int32_t n = (u >> 31) ? -(int32_t)k : (int32_t)k;
+  return exc ? std::numeric_limits<TN>::min() : (TN)n;
+}
+
+// total over every integer: |n| as uint32 (2^15 / 2^31 for the type's minimum), the exponent's carry masked
+template <typename TN>
+__device__ __forceinline__ uint32_t unprec_one(TN n, uint32_t t) {
+  const int32_t v = (int32_t)n;
+  const uint32_t mag = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+  return ((mag << t) & 0x7fffffffu) | (v < 0 ? 0x80000000u : 0u);
+}
+
+// element form: any alignment, any count.  The loop is left as written: interleaved or unrolled, a
+// grid-stride loop divides for its trip count, and the compiler does that with a floating-point
+// reciprocal -- on the index, not the data, but these kernels hold no such instruction at all; one
+// pass covers 2^24 elements, so there is little to interleave
+template <int DIR, typename TN>
+__global__ void __launch_bounds__(kThreads) prec_kernel(const void* __restrict__ x, int64_t n, void* __restrict__ out,
+                                                      uint32_t t, uint32_t rnd) {
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (DIR == KMP_ENCODE) ((TN*)out)[i] = prec_one<TN>(((const uint32_t*)x)[i], t, rnd);
+    else ((uint32_t*)out)[i] = unprec_one<TN>(((const TN*)x)[i], t);
+  }
+}
+
+// vector form: one item = four elements, a 16-byte access on the float32 side and an 8- (int16) or
+// 16-byte (int32) one on the integer side, both aligned to their size; ``n4`` items
+template <int DIR, typename TN>
+__global__ void __launch_bounds__(kThreads) prec_vec_kernel(const void* __restrict__ x, int64_t n4,
+                                                          void* __restrict__ out, uint32_t t, uint32_t rnd) {
+  using NV = typename std::conditional<sizeof(TN) == 2, u32x2v, u32x4v>::type;  // four TN
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (DIR == KMP_ENCODE) {
+      const u32x4v xv = __builtin_nontemporal_load((const u32x4v*)x + i);
+      NV ov;
+      TN* oo = (TN*)&ov;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) oo[j] = prec_one<TN>(xv[j], t, rnd);
+      __builtin_nontemporal_store(ov, (NV*)out + i);
+    } else {
+      const NV xv = __builtin_nontemporal_load((const NV*)x + i);
+      const TN* xx = (const TN*)&xv;
+      u32x4v ov;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ov[j] = unprec_one<TN>(xx[j], t);
+      __builtin_nontemporal_store(ov, (u32x4v*)out + i);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Box copy with conversion (slicing / .at[box].set of the chunk driver)
 // ------------------------------------------------------------------------------------------
@@ -738,6 +801,34 @@ int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* p
         quant_vec_kernel<DIR, TN><<<grid_for(n / 4), kThreads, 0, s>>>(x, n / 4, out, q);
       else
         quant_kernel<DIR, TN><<<grid_for(n), kThreads, 0, s>>>(x, n, out, q);
+      return check_launch("code");
+    };
+    auto with_t = [&](auto dir_c) { return ndt == KMP_I16 ? go(dir_c, int16_t{}) : go(dir_c, int32_t{}); };
+    return direction == KMP_ENCODE ? with_t(std::integral_constant<int, KMP_ENCODE>{})
+                                   : with_t(std::integral_constant<int, KMP_DECODE>{});
+  }
+  if (coder >= 0 && is_prec_code(coder_code(coder))) {
+    // float32 <-> int16 / int32 by the top m mantissa bits: no prediction either
+    const int code = coder_code(coder);
+    const int32_t field = coder >> 8;  // m + 1
+    const int ndt = code == KMP_CODER_PREC_I16 ? KMP_I16 : KMP_I32;
+    KMP_REQUIRE(!pred, "the quantising coders take no prediction (pred must be NULL)");
+    KMP_REQUIRE(field >= 1 && field <= 23, "kept mantissa bits outside [0, 22]");
+    KMP_REQUIRE(x_dtype == (direction == KMP_ENCODE ? (int)KMP_F32 : ndt),
+                "quantising coders: float32 in (encode), the code's int16 / int32 in (decode)");
+    if (n == 0) return KMP_OK;
+    KMP_REQUIRE(x && out, "null pointer");
+    const uint32_t t = (uint32_t)(24 - field), rnd = (1u << (t - 1)) - 1u;
+    hipStream_t s = (hipStream_t)stream;
+    auto go = [&](auto dir_c, auto ntag) {
+      constexpr int DIR = decltype(dir_c)::value;
+      using TN = decltype(ntag);
+      // the integer side of a vector item is 4 * sizeof(TN) bytes, the float32 side 16
+      const uintptr_t fa = (uintptr_t)(DIR == KMP_ENCODE ? x : out), na = (uintptr_t)(DIR == KMP_ENCODE ? out : x);
+      if ((fa & 15) == 0 && (na & (4 * sizeof(TN) - 1)) == 0 && n % 4 == 0)
+        prec_vec_kernel<DIR, TN><<<grid_for(n / 4), kThreads, 0, s>>>(x, n / 4, out, t, rnd);
+      else
+        prec_kernel<DIR, TN><<<grid_for(n), kThreads, 0, s>>>(x, n, out, t, rnd);
       return check_launch("code");
     };
     auto with_t = [&](auto dir_c) { return ndt == KMP_I16 ? go(dir_c, int16_t{}) : go(dir_c, int32_t{}); };

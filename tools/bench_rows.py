@@ -556,6 +556,58 @@ def main():
             print(json.dumps(line), flush=True)
         del xq, routes
 
+    # relative-error float32 coding, only when asked for: the mantissa quantisers' two
+    # kmp_code launches on the same 512 x 64^3 float32 for both integer types, alternated in one process
+    # with §17's quantisers and with a device copy that moves the same number of bytes.
+    if 'prec' in want:
+        from kompressor_amd import _device as dev
+        lib, L = kom._lib.lib, kom._lib
+        xq = (torch.randn((512, 64, 64, 64, 1), device='cuda') * 3).contiguous()
+        n = xq.numel()
+        routes, moved = {}, {}
+        for fam, tdt, param in (('prec', torch.int16, 6), ('prec', torch.int32, 10), ('quant', torch.int16, -9),
+                                ('quant', torch.int32, -20)):
+            tag = f'{fam}:{"int16" if tdt == torch.int16 else "int32"}'
+            q = torch.empty(xq.shape, dtype=tdt, device='cuda')
+            back = torch.empty_like(xq)
+            if fam == 'prec':
+                coder = L.coder_prec(L.CODER_PREC_I16 if tdt == torch.int16 else L.CODER_PREC_I32, param)
+            else:
+                coder = L.coder_quant(L.CODER_QUANT_I16 if tdt == torch.int16 else L.CODER_QUANT_I32, param)
+
+            def enc(coder=coder, q=q):
+                kom._lib.check(lib.kmp_code(L.ENCODE, coder, 0, None, L.F32, xq.data_ptr(), n, q.data_ptr(), dev.stream()), 'code')
+
+            def dec(coder=coder, q=q, back=back, code=dev.dtype_code(q)):
+                kom._lib.check(lib.kmp_code(L.DECODE, coder, 0, None, code, q.data_ptr(), n, back.data_ptr(), dev.stream()), 'code')
+            enc()
+            dec()
+            torch.cuda.synchronize()
+            assert int((q == torch.iinfo(tdt).min).sum().item()) == 0
+            err = (back.double() - xq.double()).abs()
+            if fam == 'prec':
+                assert float((err / xq.double().abs().clamp_min(2.0 ** -126)).max().item()) <= 2.0 ** -(param + 1)
+            else:
+                assert float(err.max().item()) <= 2.0 ** (param - 1)
+            del err
+            moved[tag] = n * (4 + q.element_size())
+            src = torch.empty(moved[tag] // 2, dtype=torch.uint8, device='cuda')
+            dst = torch.empty_like(src)
+            routes[tag] = {'quantise': enc, 'dequantise': dec, 'copy': lambda src=src, dst=dst: dst.copy_(src)}
+        samples = {(t, d): [] for t in routes for d in routes[t]}
+        for _ in range(9):
+            for t in routes:
+                for d in routes[t]:
+                    samples[(t, d)].append(gpu_time(routes[t][d], args.reps))
+        med = {k: float(np.median(v)) for k, v in samples.items()}
+        for (t, d), v in samples.items():
+            line = {'row': f'{t}:{d}', 'what': f'512 x 64^3 float32 <-> {t.split(":")[1]}, {moved[t]} bytes moved',
+                    'TBps': round(moved[t] / med[(t, d)] / 1e12, 3), 'us': round(med[(t, d)] * 1e6, 1),
+                    'us_min': round(min(v) * 1e6, 1), 'us_max': round(max(v) * 1e6, 1), 'samples': len(v),
+                    'ratio_to_copy': round(med[(t, d)] / med[(t, 'copy')], 4)}
+            print(json.dumps(line), flush=True)
+        del xq, routes
+
     # geometry primitives (volume/utils.py) on the C3 tile batch
     if not want or 'primitives' in want:
         hp, _ = _nd.d_pad_highres(vol, 3)                       # [512, 65^3]

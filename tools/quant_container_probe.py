@@ -2,7 +2,9 @@
 file size, bits per sample and the last_timing splits; three timed rounds, the bounds alternated within
 each.  ``--nan`` turns about 10 % of the volume (a slab of planes) into NaN: the cost of the exception
 path.  ``--lossless-only`` runs the ``None`` row alone and passes no keyword, so the same script
-measures a build from before error-bounded coding."""
+measures a build from before error-bounded coding.  ``--rel`` measures the relative mode instead
+(DESIGN.md §18): the field becomes ``10 ** (2 f)`` -- four decades -- times ``1 + noise / 15``, and the
+bounds are ``rel_error`` None, 1e-1, 1e-2, 1e-3."""
 import json, os, sys, tempfile
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,6 +20,10 @@ for _ in range(4):
     f += np.sin(2 * np.pi * (k[0] * ax[:, None, None] + k[1] * ax[None, :, None] + k[2] * ax[None, None, :]) + ph)
 f /= np.abs(f).max()
 x = (f + rng.standard_normal((n, n, n), dtype=np.float32) / 15).astype(np.float32)  # noise 1/15 of the amplitude
+REL = '--rel' in sys.argv
+KEY, MAX = ('rel_error', 'max_rel_error') if REL else ('abs_error', 'max_abs_error')
+if REL:  # multiplicative noise on a field that spans four decades
+    x = (np.power(np.float32(10), 2 * f) * (1 + rng.standard_normal((n, n, n), dtype=np.float32) / 15)).astype(np.float32)
 if '--nan' in sys.argv:
     x[200:251] = np.nan
 x = x.reshape(1, n, n, n, 1)
@@ -29,7 +35,7 @@ out = {}
 for rnd in range(4):
     for a in bounds:
         path = os.path.join(d, 'v.kmp')
-        res = container.compress(path, xt, pred, levels=3, **({} if a is None else {'abs_error': a}))
+        res = container.compress(path, xt, pred, levels=3, **({} if a is None else {KEY: a}))
         tc = dict(container.last_timing)
         torch.cuda.synchronize()
         y = container.decompress(path, as_numpy=False)
@@ -38,7 +44,9 @@ for rnd in range(4):
             assert torch.equal(y.view(torch.int32), xt.view(torch.int32))
         else:
             err = (y.double() - xt.double()).abs()
-            assert float(err[torch.isfinite(xt)].max().item()) == res['max_abs_error'] <= res['abs_error']
+            if REL:
+                err /= xt.double().abs().clamp_min(2.0 ** -126)
+            assert float(err[torch.isfinite(xt)].max().item()) == res[MAX] <= res[KEY]
             assert torch.equal(y.view(torch.int32)[~torch.isfinite(xt)], xt.view(torch.int32)[~torch.isfinite(xt)])
             del err
         del y
@@ -48,10 +56,10 @@ for rnd in range(4):
 for a, runs in out.items():
     med = lambda xs: float(np.median(xs))
     res = runs[0][0]
-    line = {'abs_error': a, 'nan_slab': '--nan' in sys.argv, 'bytes': res['bytes'],
+    line = {KEY: a, 'nan_slab': '--nan' in sys.argv, 'bytes': res['bytes'],
             'bits_per_sample': round(res['bits_per_sample'], 4),
-            **{k: res[k] for k in ('abs_error', 'max_abs_error', 'exceptions', 'quant_dtype') if k in res and a is not None},
-            'abs_error_asked': a,
+            **{k: res[k] for k in (KEY, MAX, 'exceptions', 'quant_dtype') if k in res and a is not None},
+            KEY + '_asked': a,
             'compress_ms': {k: [round(1e3 * f([r[1][k] for r in runs]), 2) for f in (med, min, max)] for k in runs[0][1]},
             'decompress_ms': {k: [round(1e3 * f([r[2][k] for r in runs]), 2) for f in (med, min, max)]
                               for k in runs[0][2] if isinstance(runs[0][2][k], float)}}
