@@ -394,6 +394,14 @@ int64_t kmp_rice_bundle_workspace_bytes(int64_t tiles_total);
 /* 2 W + 2 words, W the sample bits).  The caller writes the header [0, 80 + 128 * arrays); the    */
 /* launches write the rest up to the byte size ``total`` they store at byte 64, total <=           */
 /* payload_off + worst, and no byte at or past ``total`` (tests/test_gpu_guard_packing.py).        */
+/* MEASURING MODE, ``bundle == NULL``: the size of the bundle without producing it.  Same arrays,  */
+/* count, tile_begin, tiles_total, workspace and stream; payload_off and the records' side_off /   */
+/* toff_off / rec_off are ignored.  The call with tile_begin == 0 clears the u64 at workspace + 0; */
+/* every call adds the payload words of its tiles to it, so after the bundle's last call it holds  */
+/* exactly the payload words the encode stores at byte 56 (the bundle is then payload_off +        */
+/* pad8(4 * words) bytes).  The samples are read once; nothing else is written, nothing allocated, */
+/* no synchronisation (graph-capturable); a call without tiles returns KMP_OK after the clear.     */
+/* kmp_last_launch() names it "rice_bundle_measure" (tests/test_gpu_guard_measure.py).             */
 int kmp_rice_bundle_encode(int32_t dtype, const kmp_rice_array* arrays, int32_t count, int64_t tile_begin,
                            int64_t tiles_total, uint8_t* bundle, int64_t payload_off, void* workspace,
                            kmp_stream_t stream);

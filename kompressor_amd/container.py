@@ -11,6 +11,8 @@ sample dtype (float32 volumes travel bit-cast to uint32) and a CRC-32 of the pay
 
     info = compress(path, highres, predictor)     # pyramid encode on the GPU + Rice + one write
     highres = decompress(path)                    # read + unpack + decode on the GPU
+    info = compress(path, highres, predictor, target_bits=4)   # the finest bound that fits 4 bits per sample
+    size = compressed_size(highres, predictor, abs_error=1e-3)  # what compress would write, sized on the GPU
     save(path, lowres, encoded, predictor=...)    # an encode() result you already have
     lowres, encoded, meta = load(path)
     box = read_region(path, planes=(z0, z1), rows=(y0, y1), cols=(x0, x1), level=k)   # only the tiles the box needs
@@ -45,7 +47,7 @@ import numpy as np
 import torch
 
 from . import _device as dev
-from . import _nd, near, packing, quant
+from . import _nd, near, packing, quant, rate
 from ._lib import DECODE as _lib_decode, check as _check, coder_max_error as _lib_max_error, lib
 from .predictors import ARITH_REV, LinearPredictor, MeanPredictor
 
@@ -263,19 +265,34 @@ def _bundle(x, arrays, dims, method, tile_crc=False):
     return blob, blob.numel(), int(crc.cpu().view(torch.uint32).item()), None
 
 
+def _meta_bytes(meta, total, crc, tiles=None):
+    """The metadata as a file stores it: ``meta`` plus the bundle's length and CRC-32 (and, for a file
+    with a per-tile CRC table of ``tiles`` entries, where it lies), compact JSON padded to 8 bytes."""
+    meta = dict(meta, bundle_bytes=int(total), crc32=int(crc) & 0xffffffff)
+    if tiles is not None:
+        meta['tile_crc'] = {'offset': int(total) + (-int(total) % 8), 'tiles': int(tiles)}
+    js = json.dumps(meta, separators=(',', ':')).encode()
+    return js + b' ' * (-len(js) % 8)
+
+
+def _bound_bytes(meta, total, tiles=None):
+    """``bound_bytes``: the length of the file of ``meta`` and a bundle of ``total`` bytes (``tiles``: its
+    per-tile CRC table's entries, None without one) with the widest CRC-32, 4294967295.  The CRC is
+    stored as a decimal, so the file written is never larger than this and at most 16 bytes smaller."""
+    trailer = 0 if tiles is None else (-int(total) % 8) + 4 * int(tiles)
+    return _HEAD.size + len(_meta_bytes(meta, total, 0xffffffff, tiles)) + int(total) + trailer
+
+
 def _write(path, meta, blob, total, crc, t0, table=None, version=VERSION):
     """Header, metadata and the first ``total`` device bytes of ``blob`` to ``path``: the bundle
     crosses the link in pinned chunks (``_device.d2h_stream``), each written to the file while the
     next ones are in flight.  ``table`` (the per-tile CRCs, u32 little-endian) follows the bundle,
     8-aligned, and is recorded in the metadata as ``'tile_crc': {'offset', 'tiles'}``."""
     t1 = time.perf_counter()
-    meta = dict(meta, bundle_bytes=int(total), crc32=int(crc) & 0xffffffff)
     trailer = b''
     if table is not None:
-        meta['tile_crc'] = {'offset': int(total) + (-int(total) % 8), 'tiles': len(table) // 4}
         trailer = b'\0' * (-int(total) % 8) + table
-    js = json.dumps(meta, separators=(',', ':')).encode()
-    js += b' ' * (-len(js) % 8)
+    js = _meta_bytes(meta, total, crc, None if table is None else len(table) // 4)
     tmp = f'{path}.tmp{os.getpid()}'
     with open(tmp, 'wb') as f:
         try:  # the file's blocks allocated up front: the write then only copies (8.0 vs 10.0 ms for
@@ -495,8 +512,26 @@ def _lossless_levels(h, predictor, levels):
     return x, arrays, meta_levels, levels
 
 
+def _check_bounds(highres, max_error, abs_error, rel_error):
+    """The bounds of a ``compress`` / ``compressed_size`` call, checked before the device is touched:
+    ``(exp or None, kept mantissa bits or None)``."""
+    exp = bits = None
+    if rel_error is not None:
+        bits = quant.mantissa_bits(rel_error)
+        if max_error or abs_error is not None:
+            raise ValueError('max_error, abs_error and rel_error exclude each other')
+        quant._require_f32(highres, 'compress(rel_error=...)')
+    if abs_error is not None:
+        exp = quant.exponent(abs_error)
+        if max_error:
+            raise ValueError('abs_error (float32 samples) and max_error (8- / 16-bit integer samples) exclude each other')
+        quant._require_f32(highres, 'compress(abs_error=...)')
+    near.check_max_error(near._input_dtype(highres), max_error)
+    return exp, bits
+
+
 def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None,
-             rel_error=None):
+             rel_error=None, target_bits=None, target_ratio=None, target_mode=None):
     """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
     :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int8 / int16
     modular on the sign-mapped samples, int32 raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
@@ -520,30 +555,51 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
     quant.effective_rel(rel_error) * max(|x|, 2**-126)``, what is not finite or rounds up to infinity
     comes back bit for bit.  Checked on the device before anything is written; the file is version 6
     and the result also holds ``'rel_error'`` (the effective bound), ``'rel_error_asked'``,
-    ``'max_rel_error'``, ``'exceptions'`` and ``'quant_dtype'``."""
-    exp = bits = None
-    if rel_error is not None:  # before the device is touched
-        bits = quant.mantissa_bits(rel_error)
-        if max_error or abs_error is not None:
-            raise ValueError('max_error, abs_error and rel_error exclude each other')
-        quant._require_f32(highres, 'compress(rel_error=...)')
-    if abs_error is not None:  # before the device is touched
-        exp = quant.exponent(abs_error)
-        if max_error:
-            raise ValueError('abs_error (float32 samples) and max_error (8- / 16-bit integer samples) exclude each other')
-        quant._require_f32(highres, 'compress(abs_error=...)')
-    near.check_max_error(near._input_dtype(highres), max_error)  # before the device is touched
+    ``'max_rel_error'``, ``'exceptions'`` and ``'quant_dtype'``.
+    ``target_bits`` (bits per sample of the whole file) or ``target_ratio`` (raw bytes / file bytes), one of
+    them and none of the three bounds, ``method='rice'``: rate control (``kompressor_amd.rate``, DESIGN.md
+    §19) -- the finest bound of a ladder whose file fits ``floor(target_bits * numel / 8)`` or
+    ``floor(raw_bytes / target_ratio)`` bytes.  ``target_mode``: ``'abs'`` (default) or ``'rel'`` for
+    float32 samples, ``'near'`` for uint8 / uint16 / int8 / int16.  Each candidate is sized on the device
+    by :func:`compressed_size`; the chosen one is then written by the explicit-bound path above, so the
+    file is byte for byte that of ``abs_error = 2**(e - 1)`` / ``rel_error = 2**-(m + 1)`` /
+    ``max_error = d``, and the result is that call's plus ``'target_bytes'`` (the budget),
+    ``'bound_bytes'`` and ``'probes'`` (``[(e or m or d, bound_bytes), ...]`` in the order asked).  A
+    budget below the coarsest rung raises ValueError and writes nothing."""
+    mode = rate.check_target(near._input_dtype(highres), target_bits, target_ratio, target_mode, method, max_error,
+                             abs_error, rel_error)  # before the device is touched
+    exp, bits = _check_bounds(highres, max_error, abs_error, rel_error)  # before the device is touched
     t0 = time.perf_counter()
     packing._check_method(method)
     _check_tile_crc_method(tile_crc, method)
-    ndim, padding = predictor.ndim, predictor.padding
     h, _ = dev.to_device(highres)
+    if mode is not None:
+        return _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0)
     if max_error:
         return _compress_near(path, h, predictor, levels, method, tile_crc, int(max_error), t0)
     if exp is not None:
         return _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0)
     if bits is not None:
         return _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0)
+    return _compress_lossless(path, h, predictor, levels, method, tile_crc, t0)
+
+
+def _compress_lossless(path, h, predictor, levels, method, tile_crc, t0):
+    """:func:`compress` without a bound: the lossless pyramid, the version-3 file."""
+    p = _parts_lossless(h, predictor, levels, method)
+    blob, total, crc, table = _bundle(p['x'], p['arrays'], (), method, tile_crc)
+    nbytes = _write(path, p['meta'], blob, total, crc, t0, table)
+    raw = h.numel() * h.element_size()
+    return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
+            'levels': p['levels'], 'max_error': 0, 'max_abs_error': 0}
+
+
+# The arrays and the metadata of a file, before anything is entropy-coded: what :func:`compress` bundles
+# and writes and what :func:`compressed_size` only measures.  Each returns {'x': the coarsest lowres,
+# 'arrays': the bundle's arrays after it, 'meta', 'levels'} and its mode's own entries.
+
+def _parts_lossless(h, predictor, levels, method):
+    ndim, padding = predictor.ndim, predictor.padding
     sample = _NP_NAME[h.dtype]
     if h.dtype == torch.float32:
         h = h.view(torch.uint32)
@@ -553,23 +609,15 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
             'predictor': _predictor_meta(predictor, padding, ndim, x.dtype)}
     # one bundle: the coarsest lowres, then every level's maps finest first (no bundle dims: the
     # per-level dims live in the metadata)
-    blob, total, crc, table = _bundle(x, arrays, (), method, tile_crc)
-    nbytes = _write(path, meta, blob, total, crc, t0, table)
-    raw = h.numel() * h.element_size()
-    return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
-            'levels': levels, 'max_error': 0, 'max_abs_error': 0}
+    return {'x': x, 'arrays': arrays, 'meta': meta, 'levels': levels}
 
 
-def _compress_near(path, h, predictor, levels, method, tile_crc, max_error, t0):
-    """:func:`compress` with ``max_error > 0``: the closed loop, the bound's check, the version-4 file."""
+def _parts_near(h, predictor, levels, method, max_error):
+    """The closed loop of ``max_error > 0``; ``'restored'`` is what the file decodes to."""
     ndim, padding = predictor.ndim, predictor.padding
     levels = _auto_levels(h.shape, ndim) if levels == 'auto' else int(levels)
     _nd._require(levels >= 1, 'levels must be >= 1')
     lowres, encoded, restored = near.d_encode_pyramid(predictor, h, levels, near.coder_id(h.dtype, max_error))
-    worst = near.d_max_abs_error(restored, h)
-    if worst > max_error:
-        raise RuntimeError(f'near-lossless encode broke its bound: max |restored - highres| = {worst} > max_error = '
-                           f'{max_error}; nothing written to {path}')
     arrays, meta_levels, shape = [], [], list(h.shape)
     for maps, dims in encoded:
         arrays.extend(maps)
@@ -578,11 +626,21 @@ def _compress_near(path, h, predictor, levels, method, tile_crc, max_error, t0):
     meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'method': method,
             'sample_dtype': _NP_NAME[h.dtype], 'levels': meta_levels, 'lowres_shape': list(lowres.shape),
             'predictor': _predictor_meta(predictor, padding, ndim, h.dtype), 'max_error': max_error}
-    blob, total, crc, table = _bundle(lowres, arrays, (), method, tile_crc)
-    nbytes = _write(path, meta, blob, total, crc, t0, table, VERSION_NEAR)
+    return {'x': lowres, 'arrays': arrays, 'meta': meta, 'levels': levels, 'restored': restored}
+
+
+def _compress_near(path, h, predictor, levels, method, tile_crc, max_error, t0):
+    """:func:`compress` with ``max_error > 0``: the closed loop, the bound's check, the version-4 file."""
+    p = _parts_near(h, predictor, levels, method, max_error)
+    worst = near.d_max_abs_error(p['restored'], h)
+    if worst > max_error:
+        raise RuntimeError(f'near-lossless encode broke its bound: max |restored - highres| = {worst} > max_error = '
+                           f'{max_error}; nothing written to {path}')
+    blob, total, crc, table = _bundle(p['x'], p['arrays'], (), method, tile_crc)
+    nbytes = _write(path, p['meta'], blob, total, crc, t0, table, VERSION_NEAR)
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
-            'levels': levels, 'max_error': max_error, 'max_abs_error': worst}
+            'levels': p['levels'], 'max_error': max_error, 'max_abs_error': worst}
 
 
 def _quant_max_error(h, n, exp, exceptions):
@@ -601,29 +659,45 @@ def _quant_max_error(h, n, exp, exceptions):
     return float(worst.item())
 
 
-def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0):
-    """:func:`compress` with ``abs_error``: the quantiser, the lossless pyramid of its integers, the
-    bound's check, the version-5 file."""
+def _parts_quantised(h, predictor, levels, method, key, param, value, quantise):
+    """The quantiser (``quantise(h, value)``), the lossless pyramid of its integers ``'n'``, the
+    exceptions ``'exc'`` (``'E'`` of them) behind the maps, the metadata's ``key`` entry."""
     ndim, padding = predictor.ndim, predictor.padding
-    n, exc = quant.d_quantise(h, exp)
+    n, exc = quantise(h, value)
     x, arrays, meta_levels, levels = _lossless_levels(n, predictor, levels)
     E = 0 if exc is None else int(exc[0].numel())
-    eps = quant.effective(abs_error)
-    worst = _quant_max_error(h, n, exp, exc)
-    if not worst <= eps:
-        raise RuntimeError(f'error-bounded encode broke its bound: max |restored - highres| = {worst} > {eps} '
-                           f'(abs_error = {abs_error}); nothing written to {path}')
     if E:  # the exceptions ride behind the maps: gap words (low, high), then the bits
         arrays = [*arrays, *quant.d_gaps(exc[0]), exc[1]]
     meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'method': method,
             'sample_dtype': 'float32', 'levels': meta_levels, 'lowres_shape': list(x.shape),
             'predictor': _predictor_meta(predictor, padding, ndim, x.dtype),
-            'quant': {'exp': exp, 'dtype': _NP_NAME[n.dtype], 'exceptions': E}}
-    blob, total, crc, table = _bundle(x, arrays, (), method, tile_crc)
-    nbytes = _write(path, meta, blob, total, crc, t0, table, VERSION_QUANT)
+            key: {param: value, 'dtype': _NP_NAME[n.dtype], 'exceptions': E}}
+    return {'x': x, 'arrays': arrays, 'meta': meta, 'levels': levels, 'n': n, 'exc': exc, 'E': E}
+
+
+def _parts_quant(h, predictor, levels, method, exp):
+    return _parts_quantised(h, predictor, levels, method, 'quant', 'exp', exp, quant.d_quantise)
+
+
+def _parts_prec(h, predictor, levels, method, bits):
+    return _parts_quantised(h, predictor, levels, method, 'prec', 'bits', bits, quant.d_quantise_rel)
+
+
+def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0):
+    """:func:`compress` with ``abs_error``: the quantiser, the lossless pyramid of its integers, the
+    bound's check, the version-5 file."""
+    p = _parts_quant(h, predictor, levels, method, exp)
+    n, E = p['n'], p['E']
+    eps = quant.effective(abs_error)
+    worst = _quant_max_error(h, n, exp, p['exc'])
+    if not worst <= eps:
+        raise RuntimeError(f'error-bounded encode broke its bound: max |restored - highres| = {worst} > {eps} '
+                           f'(abs_error = {abs_error}); nothing written to {path}')
+    blob, total, crc, table = _bundle(p['x'], p['arrays'], (), method, tile_crc)
+    nbytes = _write(path, p['meta'], blob, total, crc, t0, table, VERSION_QUANT)
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
-            'levels': levels, 'abs_error': eps, 'abs_error_asked': float(abs_error), 'max_abs_error': worst,
+            'levels': p['levels'], 'abs_error': eps, 'abs_error_asked': float(abs_error), 'max_abs_error': worst,
             'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype]}
 
 
@@ -647,27 +721,95 @@ def _prec_max_error(h, n, bits, exceptions):
 def _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0):
     """:func:`compress` with ``rel_error``: the mantissa quantiser, the lossless pyramid of its integers,
     the guarantee's check, the version-6 file."""
-    ndim, padding = predictor.ndim, predictor.padding
-    n, exc = quant.d_quantise_rel(h, bits)
-    x, arrays, meta_levels, levels = _lossless_levels(n, predictor, levels)
-    E = 0 if exc is None else int(exc[0].numel())
+    p = _parts_prec(h, predictor, levels, method, bits)
+    n, E = p['n'], p['E']
     eps = quant.effective_rel(rel_error)
-    worst = _prec_max_error(h, n, bits, exc)
+    worst = _prec_max_error(h, n, bits, p['exc'])
     if not worst <= eps:
         raise RuntimeError(f'relative-error encode broke its bound: max |restored - highres| / max(|highres|, 2^-126) '
                            f'= {worst} > {eps} (rel_error = {rel_error}); nothing written to {path}')
-    if E:  # the exceptions ride behind the maps: gap words (low, high), then the bits
-        arrays = [*arrays, *quant.d_gaps(exc[0]), exc[1]]
-    meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'method': method,
-            'sample_dtype': 'float32', 'levels': meta_levels, 'lowres_shape': list(x.shape),
-            'predictor': _predictor_meta(predictor, padding, ndim, x.dtype),
-            'prec': {'bits': bits, 'dtype': _NP_NAME[n.dtype], 'exceptions': E}}
-    blob, total, crc, table = _bundle(x, arrays, (), method, tile_crc)
-    nbytes = _write(path, meta, blob, total, crc, t0, table, VERSION_PREC)
+    blob, total, crc, table = _bundle(p['x'], p['arrays'], (), method, tile_crc)
+    nbytes = _write(path, p['meta'], blob, total, crc, t0, table, VERSION_PREC)
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
-            'levels': levels, 'rel_error': eps, 'rel_error_asked': float(rel_error), 'max_rel_error': worst,
+            'levels': p['levels'], 'rel_error': eps, 'rel_error_asked': float(rel_error), 'max_rel_error': worst,
             'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype]}
+
+
+def _sized(h, predictor, levels, tile_crc, max_error=0, abs_error=None, rel_error=None):
+    """:func:`compressed_size` of the device tensor ``h`` with checked arguments."""
+    if max_error:
+        p = _parts_near(h, predictor, levels, 'rice', int(max_error))
+        own = {'max_error': int(max_error)}
+    elif abs_error is not None:
+        p = _parts_quant(h, predictor, levels, 'rice', quant.exponent(abs_error))
+        own = {'abs_error': quant.effective(abs_error), 'exceptions': p['E'], 'quant_dtype': _NP_NAME[p['n'].dtype]}
+    elif rel_error is not None:
+        p = _parts_prec(h, predictor, levels, 'rice', quant.mantissa_bits(rel_error))
+        own = {'rel_error': quant.effective_rel(rel_error), 'exceptions': p['E'], 'quant_dtype': _NP_NAME[p['n'].dtype]}
+    else:
+        p = _parts_lossless(h, predictor, levels, 'rice')
+        own = {'max_error': 0}
+    arrays = [p['x'], *p['arrays']]
+    total = packing.bundle_size(arrays)
+    tiles = packing._rice_enc_plan(arrays, ())['T'] if tile_crc else None  # the table's entries, as _bundle counts them
+    return {'bound_bytes': _bound_bytes(p['meta'], total, tiles), 'bundle_bytes': total,
+            'raw_bytes': h.numel() * h.element_size(), 'levels': p['levels'], **own}
+
+
+def compressed_size(highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None,
+                    rel_error=None):
+    """The size of the file :func:`compress` would write for the same arguments, without writing it:
+    the same argument checks, the same quantiser and pyramid (or closed loop), then the measuring
+    launches of the Rice bundle (``packing.bundle_size``: the arrays are read once, no bundle is
+    allocated, 8 bytes come back).  Returns ``{'bound_bytes', 'bundle_bytes', 'raw_bytes', 'levels'}`` and
+    the mode's own entries (``'max_error'``; ``'abs_error'`` or ``'rel_error'`` -- the effective bound --
+    with ``'exceptions'`` and ``'quant_dtype'``).  ``bundle_bytes`` is exact.  ``bound_bytes`` is the
+    file's length with the metadata's ``crc32`` at its widest, 4294967295 (the CRC is stored as a
+    decimal and is not known before the bytes exist): the file written is never larger and at most 16
+    bytes smaller.  The bound itself is not checked here (:func:`compress` checks it before it writes).
+    ``method='planes'`` raises ValueError: only Rice bundles are sized on the device."""
+    _check_bounds(highres, max_error, abs_error, rel_error)  # before the device is touched
+    packing._check_method(method)
+    if method != 'rice':
+        raise ValueError("compressed_size needs method='rice' (only Rice bundles are sized on the device)")
+    h, _ = dev.to_device(highres)
+    return _sized(h, predictor, levels, tile_crc, max_error, abs_error, rel_error)
+
+
+def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0):
+    """:func:`compress` with ``target_bits`` / ``target_ratio``: the ladder of ``mode``, the search over
+    it with :func:`compressed_size` as the size of a rung, then the chosen rung written by the
+    explicit-bound path (which still checks its bound before it writes)."""
+    raw = h.numel() * h.element_size()
+    budget = rate.budget_bytes(h.numel(), raw, target_bits, target_ratio)
+    if mode == 'abs':
+        # the largest finite |x|: one reduction on the device, one read-back
+        M = float(torch.where(torch.isfinite(h), h.abs(), torch.zeros((), device=h.device)).max().item()) if h.numel() else 0.0
+        ladder = rate.ladder_abs(M)
+    elif mode == 'rel':
+        ladder = rate.ladder_rel()
+    else:
+        ladder = rate.ladder_near(h.dtype)
+
+    def size(r):
+        key, value = rate.bound_of(mode, ladder[r])
+        return _sized(h, predictor, levels, tile_crc, **{key: value})['bound_bytes']
+    try:
+        r, probes = rate.search(size, len(ladder), budget)
+    except rate.Unreachable as e:
+        raise ValueError(f'{path}: the target of {budget} bytes cannot be met: the coarsest rung of the {mode!r} '
+                         f'ladder has bound_bytes = {e.coarsest}; nothing written') from None
+    key, value = rate.bound_of(mode, ladder[r])
+    if mode == 'abs':
+        out = _compress_quant(path, h, predictor, levels, 'rice', tile_crc, value, ladder[r], t0)
+    elif mode == 'rel':
+        out = _compress_prec(path, h, predictor, levels, 'rice', tile_crc, value, ladder[r], t0)
+    elif value:
+        out = _compress_near(path, h, predictor, levels, 'rice', tile_crc, value, t0)
+    else:  # rung 0 of the 'near' ladder is the lossless file
+        out = _compress_lossless(path, h, predictor, levels, 'rice', tile_crc, t0)
+    return dict(out, target_bytes=budget, bound_bytes=dict(probes)[r], probes=[(ladder[q], b) for q, b in probes])
 
 
 def _quant_exceptions(path, arrays, E, numel):

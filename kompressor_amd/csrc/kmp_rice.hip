@@ -257,6 +257,51 @@ __device__ __forceinline__ void quotients(const uint32_t (&w)[Sw<W>::NW], int k,
   }
 }
 
+// Pass 1 of the bundle encode for one wave step: the lane's 8 samples ``w`` -> the block's z-planes
+// ``Z`` (lane j: planes 8p + j after the byte transpose) and the block's key, the same on its 8 lanes:
+// key & 31 = k*, key >> 5 = the block's payload words, key == 64 an all-zero block.  The measuring
+// kernel's copy of the key lines of rice_bundle_encode_kernel below, statement for statement: calling
+// this helper from that kernel changed its register allocation (108 -> 109 VGPRs for 16-bit, 187 -> 190
+// for 32-bit samples, and the instruction counts with them), so that kernel keeps its lines inline.
+// S_k = sum_i (z_i >> k) = sum_{b >= k} count_b 2^(b - k) for this lane's k = 8p + j: a doubling
+// suffix sum of the plane counts over the group, plus S_{8(p+1)} (group lane 0) << (8 - j).
+// Equal to the Horner recurrence S_k = 2 S_{k+1} + count_k of the oracle (capped at kSumCap
+// for 32-bit samples: min(S_k, cap), which is what the capped recurrence yields)
+template <int W>
+__device__ __forceinline__ uint32_t block_key(const uint32_t (&w)[Sw<W>::NW], uint32_t (&Z)[Sw<W>::NP][2], int j) {
+  constexpr int NP = Sw<W>::NP;
+  uint32_t key = 0xffffffffu;
+  bool lo = false;
+  if constexpr (NP > 1) {
+    lo = __all(byte_residuals<W>(w));
+    if (lo) {
+      // every sample of the wave step in [-128, 127] (the usual residual map): z < 256, so the
+      // z-planes from 8 up are zero -- transpose and count plane group 0 only; the sign plane
+      // is plane 7; the keys of k >= 8 are those of S_k = 0
+      zplanes_lo<W>(w, Z);
+      xtr8(Z[0][0], Z[0][1], j);
+      const uint32_t sk = group8_suffix2(__builtin_popcount(Z[0][0]) + __builtin_popcount(Z[0][1]), j);
+      key = min(((sk + 95u) & ~31u) + 65u * (uint32_t)j, 64u + 65u * (uint32_t)(8 + j));
+    }
+  }
+  if (!lo) {
+    zplanes<W>(w, Z);
+#pragma unroll
+    for (int p = 0; p < NP; ++p) xtr8(Z[p][0], Z[p][1], j);
+    uint32_t above = 0;
+#pragma unroll
+    for (int p = NP - 1; p >= 0; --p) {
+      const uint32_t c = __builtin_popcount(Z[p][0]) + __builtin_popcount(Z[p][1]);
+      uint32_t sk = group8_suffix2(c, j);
+      if (p < NP - 1) sk += above << (8 - j);
+      if constexpr (W > 16) sk = min(sk, kSumCap);
+      key = min(key, ((sk + 95u) & ~31u) + 65u * (uint32_t)(8 * p + j));
+      if (p > 0) above = group8_first(sk, j);
+    }
+  }
+  return group8_min(key, j);
+}
+
 // 8- and 16-bit samples at 4 waves per SIMD (amdgpu_waves_per_eu: at most 128 VGPRs, 16-bit samples
 // spill 28 bytes): 170 vs 180 us per C3 bundle at 3 waves (137 VGPRs),
 // profiles/round4/ab_rice_waves4_r4r1.log; 32-bit samples need more registers than that
@@ -462,6 +507,60 @@ __global__ void __launch_bounds__(64 * kEncWaves) __attribute__((amdgpu_waves_pe
   // ---- the wave's payload words are contiguous: one coalesced copy out of LDS ----
   uint32_t* const dst = (uint32_t*)(blob + payload_off) + (s_excl + wbase);
   for (uint32_t i = lane; i < wtot; i += 64) dst[i] = wl[i];
+}
+
+// ---- measuring mode (rice_bundle_measure_kernel): the payload words the encode above would write
+// for the same arrays, and nothing else.  Pass 1 alone: the tile shape and lane layout of the encode
+// (wave wv of a tile takes its blocks wv * 64 .. wv * 64 + 63, 8 per step), block_key per step, the
+// words of the blocks that exist summed per lane (a block's 8 lanes agree: lane j == 0 counts it),
+// then over the wave and the workgroup, and ONE 64-bit atomic add per workgroup into ``*total``.
+// No LDS stage, no look-back, no ticket: the sum does not depend on the order of the tiles, so a
+// workgroup takes tiles blockIdx.x, blockIdx.x + gridDim.x, ...  Neither the samples nor the
+// z-planes outlive their step, and the loads are batched kMeasU steps at a time ----
+constexpr int kMeasU = 4;
+constexpr int kMeasGrid = 4096;  // workgroups at most (16 per CU): bounds the atomics per launch
+static_assert(kEncSteps % kMeasU == 0, "measure: whole load batches per wave");
+
+template <int W>
+__global__ void __launch_bounds__(64 * kEncWaves) rice_bundle_measure_kernel(RArrs A, int64_t tile_begin, int64_t tiles,
+                                                                            unsigned long long* __restrict__ total) {
+  constexpr int NP = Sw<W>::NP, NW = Sw<W>::NW;
+  constexpr int S = kEncSteps, U = kMeasU;
+  __shared__ unsigned long long wsum[kEncWaves];
+  const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, j = lane & 7, g8 = lane >> 3;
+  uint32_t acc = 0;  // <= 66 words x 8 steps per tile and lane; a launch has < 2^31 tiles, so a workgroup of a full
+                     // grid takes < 2^19 of them: below 2^29
+  for (int64_t gt = blockIdx.x; gt < tiles; gt += gridDim.x) {
+    const int64_t g = tile_begin + gt;
+    const int a = array_of(A, g);
+    const RArr& R = A.a[a];
+    const int64_t blk0 = (g - R.tile0) * kTileBlocks + wv * 8 * S;
+    if (blk0 >= R.nb) continue;  // wave-uniform: the short last tile
+#pragma unroll
+    for (int s0 = 0; s0 < S; s0 += U) {
+      uint32_t w[U][NW];
+#pragma unroll
+      for (int u = 0; u < U; ++u) load8s<W>(R.x, R.n, (blk0 + 8 * (s0 + u) + g8) * 64 + j * 8, w[u]);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const bool has = blk0 + 8 * (s0 + u) + g8 < R.nb;
+        uint32_t Z[NP][2];
+        const uint32_t key = block_key<W>(w[u], Z, j);
+        acc += (key == 64u || !has || j != 0) ? 0u : key >> 5;
+      }
+    }
+  }
+  unsigned long long sum = acc;
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+  if (lane == 0) wsum[wv] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long t = 0;
+#pragma unroll
+    for (int q = 0; q < kEncWaves; ++q) t += wsum[q];
+    if (t) atomicAdd(total, t);
+  }
 }
 
 // the lane's 8 samples from their quotients and low bits: unzigzag((q << k) | low); 16-bit samples
@@ -1007,14 +1106,14 @@ int kmp_unpack_check(int32_t format, int32_t dtype, const uint8_t* side_a, const
 int64_t kmp_rice_tiles(int64_t n) { return n > 0 ? ceil_div(kmp_pack_blocks(n), (int64_t)rc::kTileBlocks) : 0; }
 
 static int rice_arrays(const kmp_rice_array* arrays, int32_t count, int64_t tile_begin, rc::RArrs& A,
-                       int64_t& tiles) {
+                       int64_t& tiles, bool layout = true) {
   KMP_REQUIRE(arrays && count >= 1 && count <= rc::kMaxArr, "rice bundle: 1 .. 32 arrays per call");
   A.count = count;
   tiles = 0;
   for (int i = 0; i < count; ++i) {
     const kmp_rice_array& s = arrays[i];
     KMP_REQUIRE(s.n >= 0 && (s.n == 0 || s.samples), "rice bundle: bad array");
-    KMP_REQUIRE(s.side_off >= 0 && s.toff_off % 8 == 0 && s.rec_off % 8 == 0, "rice bundle: bad layout");
+    KMP_REQUIRE(!layout || (s.side_off >= 0 && s.toff_off % 8 == 0 && s.rec_off % 8 == 0), "rice bundle: bad layout");
     rc::RArr& r = A.a[i];
     r.x = s.samples;
     r.n = s.n;
@@ -1034,12 +1133,25 @@ int kmp_rice_bundle_encode(int32_t dtype, const kmp_rice_array* arrays, int32_t 
                            kmp_stream_t stream) {
   const int W = pk::sample_bits(dtype);
   KMP_REQUIRE(W > 0, "rice bundle: unsupported dtype");
-  KMP_REQUIRE(bundle && workspace && payload_off % 8 == 0 && tile_begin >= 0 && tiles_total >= 0,
+  KMP_REQUIRE(workspace && (!bundle || payload_off % 8 == 0) && tile_begin >= 0 && tiles_total >= 0,
               "rice bundle: bad argument");
   rc::RArrs A{};
   int64_t tiles = 0;
-  if (int st = rice_arrays(arrays, count, tile_begin, A, tiles)) return st;
+  if (int st = rice_arrays(arrays, count, tile_begin, A, tiles, bundle != nullptr)) return st;
   KMP_REQUIRE(tile_begin + tiles <= tiles_total, "rice bundle: tiles past the total");
+  if (!bundle) {  // measuring mode: the payload words of these tiles added to the u64 at workspace + 0
+    unsigned long long* total = (unsigned long long*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    if (tile_begin == 0 && hipMemsetAsync(total, 0, sizeof(*total), s) != hipSuccess)
+      return fail(KMP_ERR_LAUNCH, "rice bundle: memset");
+    if (tiles == 0) return KMP_OK;
+    KMP_REQUIRE(tiles < ((int64_t)1 << 31), "rice bundle: too many tiles in one call");
+    const unsigned grid = (unsigned)(tiles < rc::kMeasGrid ? tiles : rc::kMeasGrid);
+    if (W == 8) rc::rice_bundle_measure_kernel<8><<<grid, 64 * rc::kEncWaves, 0, s>>>(A, tile_begin, tiles, total);
+    else if (W == 16) rc::rice_bundle_measure_kernel<16><<<grid, 64 * rc::kEncWaves, 0, s>>>(A, tile_begin, tiles, total);
+    else rc::rice_bundle_measure_kernel<32><<<grid, 64 * rc::kEncWaves, 0, s>>>(A, tile_begin, tiles, total);
+    return check_launch("rice_bundle_measure");
+  }
   uint64_t* state = (uint64_t*)workspace;
   unsigned* ticket = (unsigned*)(state + tiles_total);
   hipStream_t s = (hipStream_t)stream;

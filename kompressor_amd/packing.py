@@ -22,6 +22,7 @@ specifications ("parity unpinned" by the reference).
     x2 = unpack(blob)                                 # bit-identical, same dtype and shape
     blob = pack_encoded(lowres, (maps, dims)[, method])  # a whole encode() result
     lowres, (maps, dims) = unpack_encoded(blob)
+    nbytes = encoded_size(lowres, (maps, dims))       # len(pack_encoded(...)) without packing ('rice')
 
 Blobs are device uint8 tensors for torch inputs and numpy uint8 arrays for numpy inputs.
 
@@ -351,6 +352,45 @@ def _rice_encode_launch(arrays, dims):
             check(lib.kmp_rice_bundle_encode(code, arr, count, tile_begin, plan['T'], out.data_ptr(), poff,
                                              ws.data_ptr(), dev.stream()), 'rice bundle')
     return out, poff, plan['T'] > 0, ts
+
+
+def _rice_measure_launch(arrays, dims):
+    """The measuring launches of a bundle (kmp_rice_bundle_encode with a NULL bundle: one per run of
+    same-dtype arrays, the runs and tile numbering of :func:`_rice_encode_launch`): ``(payload offset,
+    the workspace whose first 8 bytes receive the payload words or None without samples, objects the
+    queued work still reads)``.  No output buffer, no synchronisation."""
+    ts = [dev.to_device(a)[0] for a in arrays]
+    plan = _rice_enc_plan(ts, dims)
+    if not plan['T']:
+        return plan['poff'], None, ts
+    ws = dev.empty((plan['ws_bytes'],), torch.uint8)
+    for first, count, tile_begin, code in plan['runs']:
+        arr = _rice_arrays_n(plan['ns'], plan['offs'], first, count, [t.data_ptr() for t in ts])
+        check(lib.kmp_rice_bundle_encode(code, arr, count, tile_begin, plan['T'], None, 0, ws.data_ptr(),
+                                         dev.stream()), 'rice bundle')
+    return plan['poff'], ws, ts
+
+
+def bundle_size(arrays, dims=()):
+    """The bytes of the 'rice' bundle of ``arrays`` -- ``_rice_pack_bundle(arrays, dims).numel()``,
+    that is ``payload_off + pad8(4 * payload words)`` -- without producing it: the samples are read
+    once by the measuring launches, nothing is written but their sum, and 8 bytes come back."""
+    poff, ws, keep = _rice_measure_launch(arrays, dims)
+    if ws is None:
+        return poff
+    words = struct.unpack('<Q', _head_bytes(ws[:8], 8))[0]  # the one synchronisation
+    del keep
+    return poff + _pad8(4 * words)
+
+
+def encoded_size(lowres, encoded, method='rice'):
+    """``len(pack_encoded(lowres, encoded))`` without packing (``method='rice'`` only: a 'planes' blob
+    has no measuring launch)."""
+    _check_method(method)
+    if method != 'rice':
+        raise ValueError("encoded_size needs method='rice'")
+    maps, dims = encoded
+    return bundle_size((lowres, *maps), dims)
 
 
 def _rice_unpack_bundle(b, hb):

@@ -608,6 +608,66 @@ def main():
             print(json.dumps(line), flush=True)
         del xq, routes
 
+    # The measuring mode of the Rice bundle encode (only with --rows measure): the
+    # launches of kmp_rice_bundle_encode with a NULL bundle against the same launches with one, on the
+    # same arrays and preallocated buffers (no allocation, no host synchronisation inside the timed
+    # calls), alternated in one process: the C3 pyramid level of 512 x 64^3 16-bit tiles (lowres + 7
+    # maps) and the 2-level int32 pyramid of a quantised 512^3 float32 field.
+    if 'measure' in want:
+        from kompressor_amd import _device as dev, container, packing, quant
+        lib = kom._lib.lib
+        zz, yy, xx = torch.meshgrid(*[torch.arange(512, device='cuda', dtype=torch.float32)] * 3, indexing='ij')
+        field = (torch.sin(xx / 41.0) * torch.cos(yy / 29.0) + torch.sin(zz / 53.0 + xx / 97.0)
+                 + 1.5 * torch.exp(-((xx - 200) ** 2 + (yy - 300) ** 2 + (zz - 250) ** 2) / (2 * 90.0 ** 2)))
+        del zz, yy, xx
+        gen = torch.Generator(device='cuda').manual_seed(0)
+        noisy = field + 4.0 / 9000.0 * torch.randn(field.shape, device='cuda', generator=gen)
+        del field
+        pred = kom.MeanPredictor(0, 3)
+        u16 = (4000 + 9000 * (noisy - noisy.min()) / (noisy.max() - noisy.min())).round().to(torch.int32).to(torch.uint16)
+        tiles = u16.view(8, 64, 8, 64, 8, 64).permute(0, 2, 4, 1, 3, 5).reshape(512, 64, 64, 64, 1).contiguous()
+        lo, (maps, _) = V.encode(pred, V.encode_values_uint16, tiles)
+        n32, exc = quant.d_quantise(noisy.reshape(1, 512, 512, 512, 1).contiguous(), -24)
+        assert n32.dtype == torch.int32 and exc is None
+        x32, arrays32, _, _ = container._lossless_levels(n32, pred, 2)
+        del noisy, u16, tiles
+        work = {'c3_16bit': [lo, *maps], 'f512_int32': [x32, *arrays32]}
+        routes, nbytes, sizes = {}, {}, {}
+        for tag, ts in work.items():
+            plan = packing._rice_enc_plan(ts, ())
+            out = torch.empty(plan['poff'] + plan['worst'] + 8, dtype=torch.uint8, device='cuda')
+            out[:plan['head']].copy_(plan['hdr'])
+            ws = torch.empty(plan['ws_bytes'], dtype=torch.uint8, device='cuda')
+
+            def launch(bundle, plan=plan, ts=ts, ws=ws):
+                for first, count, tile_begin, code in plan['runs']:
+                    arr = packing._rice_arrays_n(plan['ns'], plan['offs'], first, count, [t.data_ptr() for t in ts])
+                    kom._lib.check(lib.kmp_rice_bundle_encode(code, arr, count, tile_begin, plan['T'], bundle, plan['poff'],
+                                                              ws.data_ptr(), dev.stream()), 'rice bundle')
+            launch(None)
+            torch.cuda.synchronize()
+            words = int(ws[:8].view(torch.int64).item())
+            launch(out.data_ptr())
+            torch.cuda.synchronize()
+            assert words == int(out[56:64].view(torch.int64).item()), 'the measured words are not the encode\'s'
+            nbytes[tag] = sum(t.numel() * t.element_size() for t in ts)
+            sizes[tag] = plan['poff'] + (4 * words + 7) // 8 * 8
+            routes[tag] = {'encode': lambda launch=launch, out=out: launch(out.data_ptr()),
+                           'measure': lambda launch=launch: launch(None)}
+        samples = {(t, d): [] for t in routes for d in routes[t]}
+        for _ in range(9):
+            for t in routes:
+                for d in routes[t]:
+                    samples[(t, d)].append(gpu_time(routes[t][d], args.reps))
+        med = {k: float(np.median(v)) for k, v in samples.items()}
+        for (t, d), v in samples.items():
+            line = {'row': f'measure:{t}:{d}', 'what': f'{len(work[t])} arrays, {nbytes[t]} sample bytes, bundle {sizes[t]} bytes',
+                    'TBps_read': round(nbytes[t] / med[(t, d)] / 1e12, 3), 'us': round(med[(t, d)] * 1e6, 1),
+                    'us_min': round(min(v) * 1e6, 1), 'us_max': round(max(v) * 1e6, 1), 'samples': len(v),
+                    'ratio_to_encode': round(med[(t, d)] / med[(t, 'encode')], 4)}
+            print(json.dumps(line), flush=True)
+        del work, routes
+
     # geometry primitives (volume/utils.py) on the C3 tile batch
     if not want or 'primitives' in want:
         hp, _ = _nd.d_pad_highres(vol, 3)                       # [512, 65^3]

@@ -4,7 +4,9 @@ each.  ``--nan`` turns about 10 % of the volume (a slab of planes) into NaN: the
 path.  ``--lossless-only`` runs the ``None`` row alone and passes no keyword, so the same script
 measures a build from before error-bounded coding.  ``--rel`` measures the relative mode instead
 (DESIGN.md §18): the field becomes ``10 ** (2 f)`` -- four decades -- times ``1 + noise / 15``, and the
-bounds are ``rel_error`` None, 1e-1, 1e-2, 1e-3."""
+bounds are ``rel_error`` None, 1e-1, 1e-2, 1e-3.  ``--target`` measures rate control instead (DESIGN.md
+§19): ``compress(target_bits=4 / 8)`` against ``compress(abs_error=the chosen bound)``, the probes it
+made and the time of one probe."""
 import json, os, sys, tempfile
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -32,6 +34,37 @@ pred = kom.MeanPredictor(0, 3)
 d = tempfile.mkdtemp(dir='/dev/shm' if os.path.isdir('/dev/shm') else None)
 bounds = (None,) if '--lossless-only' in sys.argv else (None, 1e-1, 1e-2, 1e-3)
 out = {}
+if '--target' in sys.argv:
+    # rate control: compress(target_bits=b) against compress(abs_error=chosen) on the same
+    # field, alternated over three timed rounds; the probe count and the device time of one probe
+    # (compressed_size at the chosen rung, synchronised)
+    import time
+    path = os.path.join(d, 'v.kmp')
+    for bits in (4.0, 8.0):
+        rows = {'target': [], 'explicit': [], 'probe': []}
+        for rnd in range(4):
+            res = container.compress(path, xt, pred, levels=3, target_bits=bits)
+            tt = dict(container.last_timing)
+            target_bytes = open(path, 'rb').read()
+            ex = container.compress(path, xt, pred, levels=3, abs_error=res['abs_error'])
+            te = dict(container.last_timing)
+            assert open(path, 'rb').read() == target_bytes and res['bits_per_sample'] <= bits
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            sized = container.compressed_size(xt, pred, levels=3, abs_error=res['abs_error'])
+            torch.cuda.synchronize()
+            tp = time.perf_counter() - t0
+            assert sized['bound_bytes'] == res['bound_bytes']
+            if rnd:
+                rows['target'].append(tt['total']); rows['explicit'].append(te['total']); rows['probe'].append(tp)
+        stat = lambda xs: [round(1e3 * f(xs), 2) for f in (lambda v: float(np.median(v)), min, max)]
+        print(json.dumps({'target_bits': bits, 'abs_error': res['abs_error'], 'bits_per_sample': round(res['bits_per_sample'], 4),
+                          'bytes': res['bytes'], 'target_bytes': res['target_bytes'], 'bound_bytes': res['bound_bytes'],
+                          'probes': len(res['probes']), 'probe_rungs': [p[0] for p in res['probes']],
+                          'target_total_ms': stat(rows['target']), 'explicit_total_ms': stat(rows['explicit']),
+                          'one_probe_ms': stat(rows['probe'])}), flush=True)
+    os.remove(path)
+    sys.exit(0)
 for rnd in range(4):
     for a in bounds:
         path = os.path.join(d, 'v.kmp')
