@@ -79,11 +79,41 @@ typedef enum {
      NULL and ``pred_dtype`` is not read.  A non-NULL pred, a field (m + 1) outside [1, 23] -- a bare
      8 or 9 included --, an x_dtype that does not fit, or these codes on any other entry point:
      KMP_ERR_ARG. */
-  KMP_CODER_PREC_I16 = 8, KMP_CODER_PREC_I32 = 9
+  KMP_CODER_PREC_I16 = 8, KMP_CODER_PREC_I32 = 9,
+  /* Error statistics of a restored array against its original (kmp_code alone, KMP_ENCODE alone;
+     DESIGN.md §20).  It codes nothing: ``x`` is the original, ``pred`` the restored array (non-NULL),
+     both of ``x_dtype`` == ``pred_dtype``, one of KMP_F32, KMP_U8, KMP_U16, KMP_I8, KMP_I16, and ``out`` an
+     8-byte aligned device buffer of KMP_COMPARE_BYTES.  The ``coder`` argument carries
+     KMP_CODER_COMPARE_MODE(continue).
+       float32: element i is COMPARED iff x_i and r_i are both finite; otherwise it is a MISMATCH iff
+       their 32-bit patterns differ (a NaN or an infinity restored bit for bit is neither).  Integer
+       samples: every element is compared, there are no mismatches.
+     Over the compared elements, e_i = (double)r_i - (double)x_i, a RECORD is eight 64-bit words:
+       0  count (u64)                       1  mismatch (u64)
+       2  max |e_i| (f64 bits; 0.0 when count == 0)
+       3  sum e_i^2 (float32 samples: f64 bits; integer samples: u64, exact)
+       4, 5  min / max of the compared x_i (f64 bits, a zero as +0.0; +inf / -inf when count == 0)
+       6, 7  0
+     After the call ``out + 0`` holds the record and ``out + 64 (1 + g)`` the partial record of workgroup g
+     for the min(KMP_COMPARE_GROUPS, ceil(items / 256)) workgroups that ran (an item: 16 bytes of each
+     array when both are 16-byte aligned and n is a multiple of 16 / sizeof(sample), else one
+     element); the rest of ``out`` is untouched.  Mode 0 starts a record; mode 1 CONTINUES the record
+     already at ``out + 0``: it is folded in first, then the partials in index order, so a caller walks a
+     large array slab by slab with one read-back and no host combine.  Every word but the float32
+     sum is the same on every device and in any order; the float32 sum is a fixed tree (lanes, waves,
+     workgroups in index order): the same buffers, count and alignment give the same 64 bits on every
+     call.  Two launches on ``stream``, no atomics.  KMP_ERR_ARG, with nothing launched: a NULL pred
+     (whatever the count), KMP_DECODE, a mode field other than 0 / 1, differing or unsupported dtypes, a
+     misaligned ``out``, 16-bit samples with n >= 2^32 (the u64 sum could overflow), or this code on
+     any other entry point.  kmp_last_launch() names it "compare". */
+  KMP_CODER_COMPARE = 10
 } kmp_coder;
 #define KMP_CODER_NEAR(code, max_error) ((code) | ((max_error) << 8))
 #define KMP_CODER_QUANT(code, exp) ((code) | (((exp) + 127) << 8))
 #define KMP_CODER_PREC(code, m) ((code) | (((m) + 1) << 8))
+#define KMP_CODER_COMPARE_MODE(cont) (KMP_CODER_COMPARE | ((cont) << 8))
+#define KMP_COMPARE_GROUPS 1024
+#define KMP_COMPARE_BYTES (64 * (1 + KMP_COMPARE_GROUPS))
 typedef enum { KMP_ENCODE = 0, KMP_DECODE = 1 } kmp_direction;
 
 typedef enum {
@@ -292,7 +322,9 @@ int kmp_tiles(int32_t nsp, int32_t dtype, int32_t direction, const void* src, co
    clamped to the sample type's range).  The output is the unsigned map (encode) or the samples'
    bit patterns (decode).
    Quantisers (KMP_CODER_QUANT and KMP_CODER_PREC, see kmp_coder): ``pred`` is NULL; float32 ->
-   int16 / int32 (ENCODE), int16 / int32 -> float32 (DECODE). */
+   int16 / int32 (ENCODE), int16 / int32 -> float32 (DECODE).
+   KMP_CODER_COMPARE (see kmp_coder): ``x`` the original, ``pred`` the restored array of the same dtype,
+   ``out`` the KMP_COMPARE_BYTES of the error statistics; ENCODE alone. */
 int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* pred, int32_t x_dtype,
              const void* x, int64_t n, void* out, kmp_stream_t stream);
 

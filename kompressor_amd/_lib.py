@@ -57,6 +57,18 @@ def coder_prec(code, m):
     return int(code) | ((int(m) + 1) << 8)
 
 
+# error statistics of a restored array against its original (kmp_code alone, ENCODE alone): the argument
+# carries coder_compare(continue); ``out`` is COMPARE_BYTES -- the record, then COMPARE_GROUPS partial records
+CODER_COMPARE = 10
+COMPARE_GROUPS = 1024
+COMPARE_BYTES = 64 * (1 + COMPARE_GROUPS)
+
+
+def coder_compare(cont=False):
+    """KMP_CODER_COMPARE_MODE(cont): start a record (False) or continue the one already in ``out``."""
+    return CODER_COMPARE | (int(bool(cont)) << 8)
+
+
 def coder_code(coder):
     return int(coder) & 0xff
 

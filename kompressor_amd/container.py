@@ -47,7 +47,7 @@ import numpy as np
 import torch
 
 from . import _device as dev
-from . import _nd, near, packing, quant, rate
+from . import _nd, metrics, near, packing, quant, rate
 from ._lib import DECODE as _lib_decode, check as _check, coder_max_error as _lib_max_error, lib
 from .predictors import ARITH_REV, LinearPredictor, MeanPredictor
 
@@ -531,7 +531,7 @@ def _check_bounds(highres, max_error, abs_error, rel_error):
 
 
 def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None,
-             rel_error=None, target_bits=None, target_ratio=None, target_mode=None):
+             rel_error=None, target_bits=None, target_ratio=None, target_mode=None, target_psnr=None):
     """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
     :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int8 / int16
     modular on the sign-mapped samples, int32 raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
@@ -565,14 +565,26 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
     file is byte for byte that of ``abs_error = 2**(e - 1)`` / ``rel_error = 2**-(m + 1)`` /
     ``max_error = d``, and the result is that call's plus ``'target_bytes'`` (the budget),
     ``'bound_bytes'`` and ``'probes'`` (``[(e or m or d, bound_bytes), ...]`` in the order asked).  A
-    budget below the coarsest rung raises ValueError and writes nothing."""
+    budget below the coarsest rung raises ValueError and writes nothing.
+    ``target_psnr`` (dB; alone of the targets and bounds, any ``method``): a quality target --
+    the COARSEST bound of the same ladders (``target_mode`` as above) whose PSNR, measured on the device
+    against the value range (float32) or ``2^W - 1`` (integer samples), is at least the target; a probe is
+    the quantiser (or the closed loop) and the comparing launch, no pyramid and no sizing for float32.
+    The chosen rung is written by the explicit-bound path, so the file is byte for byte that call's and
+    the result is that call's plus ``'target_psnr'`` and ``'probes'`` (``[(e or m or d, psnr), ...]`` in the
+    order asked).  A target above the finest rung's PSNR raises ValueError and writes nothing.
+    Quality figures: every lossy result also holds ``'mse'``, ``'psnr'`` and ``'value_range'``, measured by
+    ``kom.metrics`` on exactly what :func:`decompress` returns (NaNs and infinities, which come back bit for
+    bit, are not compared); a lossless one holds ``'mse': 0.0`` and ``'psnr': inf``."""
     mode = rate.check_target(near._input_dtype(highres), target_bits, target_ratio, target_mode, method, max_error,
-                             abs_error, rel_error)  # before the device is touched
+                             abs_error, rel_error, target_psnr)  # before the device is touched
     exp, bits = _check_bounds(highres, max_error, abs_error, rel_error)  # before the device is touched
     t0 = time.perf_counter()
     packing._check_method(method)
     _check_tile_crc_method(tile_crc, method)
     h, _ = dev.to_device(highres)
+    if target_psnr is not None:
+        return _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, float(target_psnr), t0)
     if mode is not None:
         return _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0)
     if max_error:
@@ -591,7 +603,7 @@ def _compress_lossless(path, h, predictor, levels, method, tile_crc, t0):
     nbytes = _write(path, p['meta'], blob, total, crc, t0, table)
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
-            'levels': p['levels'], 'max_error': 0, 'max_abs_error': 0}
+            'levels': p['levels'], 'max_error': 0, 'max_abs_error': 0, 'mse': 0.0, 'psnr': float('inf')}
 
 
 # The arrays and the metadata of a file, before anything is entropy-coded: what :func:`compress` bundles
@@ -640,7 +652,35 @@ def _compress_near(path, h, predictor, levels, method, tile_crc, max_error, t0):
     nbytes = _write(path, p['meta'], blob, total, crc, t0, table, VERSION_NEAR)
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
-            'levels': p['levels'], 'max_error': max_error, 'max_abs_error': worst}
+            'levels': p['levels'], 'max_error': max_error, 'max_abs_error': worst,
+            **_quality(metrics.d_compare(h.reshape(-1), p['restored'].reshape(-1)), h.dtype)}
+
+
+def _restored_record(h, n, dequantise, exceptions):
+    """The comparing call (``metrics.d_compare``) of the float32 device tensor ``h`` against exactly what
+    :func:`decompress` returns for the quantised ``n``: slab by slab -- ``dequantise(slab of n)``, the slab's
+    exceptions put back, the comparison continuing one record -- so the temporaries stay bounded.
+    Returns the device record (None for an empty array); nothing is read back but, when there are
+    exceptions, the slabs' positions in the index list (once)."""
+    hf, nf = h.reshape(-1), n.reshape(-1)
+    cuts = [*range(0, hf.numel(), _QUANT_SLAB), hf.numel()]
+    if exceptions is not None:
+        idx, bits = exceptions
+        at = torch.searchsorted(idx, torch.tensor(cuts, device='cuda')).tolist()
+    record = None
+    for k, (s, e) in enumerate(zip(cuts, cuts[1:])):
+        r = dequantise(nf[s:e])
+        if exceptions is not None and at[k + 1] > at[k]:
+            r.view(torch.int32)[idx[at[k]:at[k + 1]] - s] = bits[at[k]:at[k + 1]].view(torch.int32)
+        record = metrics.d_compare(hf[s:e], r, record)
+    return record
+
+
+def _quality(record, dtype, peak=None):
+    """``{'mse', 'psnr', 'value_range'}`` of a device record (one read-back; None: nothing compared)."""
+    words = metrics.record_words(record) if record is not None else metrics._empty_words()
+    q = metrics.summary(words, dtype, peak)
+    return {'mse': q['mse'], 'psnr': q['psnr'], 'value_range': q['value_range']}
 
 
 def _quant_max_error(h, n, exp, exceptions):
@@ -698,7 +738,8 @@ def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
             'levels': p['levels'], 'abs_error': eps, 'abs_error_asked': float(abs_error), 'max_abs_error': worst,
-            'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype]}
+            'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype],
+            **_quality(_restored_record(h, n, lambda s: quant.d_code(_lib_decode, n.dtype, exp, s), p['exc']), h.dtype)}
 
 
 def _prec_max_error(h, n, bits, exceptions):
@@ -733,7 +774,9 @@ def _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
             'levels': p['levels'], 'rel_error': eps, 'rel_error_asked': float(rel_error), 'max_rel_error': worst,
-            'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype]}
+            'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype],
+            **_quality(_restored_record(h, n, lambda s: quant.d_code_rel(_lib_decode, n.dtype, bits, s), p['exc']),
+                       h.dtype)}
 
 
 def _sized(h, predictor, levels, tile_crc, max_error=0, abs_error=None, rel_error=None):
@@ -810,6 +853,67 @@ def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, ta
     else:  # rung 0 of the 'near' ladder is the lossless file
         out = _compress_lossless(path, h, predictor, levels, 'rice', tile_crc, t0)
     return dict(out, target_bytes=budget, bound_bytes=dict(probes)[r], probes=[(ladder[q], b) for q, b in probes])
+
+
+def _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, target, t0):
+    """:func:`compress` with ``target_psnr``: the ladder of ``mode``, ``rate.search_quality`` over it with the
+    PSNR of a rung measured on the device -- float32: the quantiser, then restore and compare in slabs;
+    integer samples: the closed loop's restored array against the input -- then the chosen rung written
+    by the explicit-bound path (which still checks its bound before it writes).  The peak is fixed once."""
+    if mode == 'near':
+        ladder, peak = rate.ladder_near(h.dtype), float(2 ** (8 * h.element_size()) - 1)
+    else:
+        # the range of the finite values and the largest finite |x|: one comparing call of h with itself
+        words = metrics.record_words(metrics.d_compare(h.reshape(-1), h.reshape(-1)))
+        peak = metrics.summary(words, h.dtype)['value_range']
+        M = float(np.abs(words.view(np.float64)[4:6]).max()) if words[0] else 0.0
+        ladder = rate.ladder_abs(M) if mode == 'abs' else rate.ladder_rel()
+
+    def psnr(r):
+        if mode == 'near':
+            if ladder[r] == 0:
+                return float('inf')
+            restored = _parts_near(h, predictor, levels, method, int(ladder[r]))['restored']
+            record = metrics.d_compare(h.reshape(-1), restored.reshape(-1))
+        elif mode == 'abs':
+            n, exc = quant.d_quantise(h, ladder[r])
+            record = _restored_record(h, n, lambda s: quant.d_code(_lib_decode, n.dtype, ladder[r], s), exc)
+        else:
+            n, exc = quant.d_quantise_rel(h, ladder[r])
+            record = _restored_record(h, n, lambda s: quant.d_code_rel(_lib_decode, n.dtype, ladder[r], s), exc)
+        return _quality(record, h.dtype, peak if peak > 0 else None)['psnr']
+    try:
+        r, probes = rate.search_quality(psnr, len(ladder), target)
+    except rate.Unreachable as e:
+        raise ValueError(f'{path}: target_psnr = {target} dB cannot be met: the finest rung of the {mode!r} ladder '
+                         f'reaches {e.finest} dB; nothing written') from None
+    key, value = rate.bound_of(mode, ladder[r])
+    if mode == 'abs':
+        out = _compress_quant(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0)
+    elif mode == 'rel':
+        out = _compress_prec(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0)
+    elif value:
+        out = _compress_near(path, h, predictor, levels, method, tile_crc, value, t0)
+    else:  # rung 0 of the 'near' ladder is the lossless file
+        out = _compress_lossless(path, h, predictor, levels, method, tile_crc, t0)
+    return dict(out, target_psnr=target, probes=[(ladder[q], v) for q, v in probes])
+
+
+def compare(path, highres, peak=None):
+    """The quality of the file ``path`` against the array ``highres`` it was made from: :func:`decompress` on
+    the device, then ``metrics.compare`` -- ``{'count', 'mismatch', 'max_abs_error', 'mse', 'rmse', 'psnr',
+    'nrmse', 'value_range', 'peak'}``.  A shape that is not the file's is ValueError, a dtype that is not
+    the file's TypeError, a bad ``peak`` ValueError: all before the device is touched."""
+    peak = metrics.check_peak(peak)
+    what = info(path)
+    dt = near._input_dtype(highres)
+    name = _NP_NAME.get(dt) if isinstance(dt, torch.dtype) else np.dtype(dt).name
+    if name != what['sample_dtype']:
+        raise TypeError(f'{path} holds {what["sample_dtype"]} samples, the array passed {name}')
+    if tuple(highres.shape) != tuple(what['shape']):
+        raise ValueError(f'{path} holds an array of shape {tuple(what["shape"])}, the array passed has {tuple(highres.shape)}')
+    metrics.check_pair(highres, highres, 'container.compare')  # a dtype that is not compared (int32, uint32): TypeError
+    return metrics.compare(highres, decompress(path, as_numpy=False), peak)
 
 
 def _quant_exceptions(path, arrays, E, numel):

@@ -125,4 +125,9 @@ static inline ZRollPlan plan_zroll(int64_t B, const Ext3& frame, int nsp) {
 int launch_maps_from_cell_means(int nsp, int dtype, const void* cm, int64_t B, const Ext3& cells, int64_t C,
                                 const MapPtrs& outs, int64_t total, bool small, hipStream_t stream);
 
+// kmp_compare.hip: the error statistics of ``r`` against ``x`` (KMP_CODER_COMPARE; n >= 1 elements of
+// ``dtype``, ``out`` the 8-byte aligned KMP_COMPARE_BYTES, ``cont`` = continue the record at its start).
+// Two launches, named "compare"; KMP_ERR_ARG for a dtype it does not take.
+int launch_compare(int dtype, const void* x, const void* r, int64_t n, void* out, int cont, hipStream_t stream);
+
 }  // namespace kmp

@@ -778,6 +778,21 @@ int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* p
              int64_t n, void* out, kmp_stream_t stream) {
   KMP_REQUIRE(direction == KMP_ENCODE || direction == KMP_DECODE, "bad direction");
   KMP_REQUIRE(n >= 0, "negative count");
+  if (coder >= 0 && coder_code(coder) == KMP_CODER_COMPARE) {
+    // error statistics (kmp_compare.hip): x the original, pred the restored array, nothing coded
+    const int32_t field = coder >> 8;  // 0: start a record, 1: continue the one at out
+    KMP_REQUIRE(pred, "compare: pred is the restored array (must not be NULL)");
+    KMP_REQUIRE(direction == KMP_ENCODE, "compare: KMP_ENCODE alone");
+    KMP_REQUIRE(field == 0 || field == 1, "compare: the mode field is 0 (start) or 1 (continue)");
+    KMP_REQUIRE(pred_dtype == x_dtype, "compare: both arrays in one dtype");
+    KMP_REQUIRE(x_dtype == KMP_F32 || x_dtype == KMP_U8 || x_dtype == KMP_U16 || x_dtype == KMP_I8 || x_dtype == KMP_I16,
+                "compare takes float32, uint8, uint16, int8 or int16 samples");
+    KMP_REQUIRE(((uintptr_t)out & 7) == 0, "compare: out must be 8-byte aligned");
+    KMP_REQUIRE(dtype_size(x_dtype) != 2 || n < ((int64_t)1 << 32), "compare: 16-bit samples take n < 2^32");
+    if (n == 0) return KMP_OK;
+    KMP_REQUIRE(x && out, "null pointer");
+    return launch_compare(x_dtype, x, pred, n, out, field, (hipStream_t)stream);
+  }
   if (coder >= 0 && is_quant_code(coder_code(coder))) {
     // float32 <-> int16 / int32 on a power-of-two step: no prediction, so none may be passed
     const int code = coder_code(coder);

@@ -19,6 +19,9 @@ Ladders (``mode``):
 
 The search assumes nothing about the sizes being monotone in the rung: it returns a rung that fits
 whose finer neighbour does not (or rung 0), after at most ``2 + ceil(log2 L)`` probes.
+
+A quality target (``target_psnr``) runs over the same ladders the other way round:
+:func:`search_quality` returns a rung that meets the target whose coarser neighbour does not.
 """
 
 import math
@@ -43,32 +46,32 @@ def _positive_finite(name, v):
 
 
 def check_target(dtype, target_bits, target_ratio, target_mode, method='rice', max_error=0, abs_error=None,
-                 rel_error=None):
-    """The arguments of a rate-controlled ``compress``, checked on the host alone.  Returns None when no
-    target is given (``target_mode`` must then be None too), else the mode: the dtype's default or
-    ``target_mode``.  ValueError: both targets, a target that is no positive finite number, a target
-    together with a bound, a method other than 'rice', an unknown mode or one that does not fit the
-    dtype; TypeError: a sample dtype without a lossy mode."""
-    if target_bits is None and target_ratio is None:
+                 rel_error=None, target_psnr=None):
+    """The arguments of a rate- or quality-controlled ``compress``, checked on the host alone.  Returns None
+    when no target is given (``target_mode`` must then be None too), else the mode: the dtype's default or
+    ``target_mode``.  ValueError: more than one target, a target that is no positive finite number, a
+    target together with a bound, a size target with a method other than 'rice', an unknown mode or one
+    that does not fit the dtype; TypeError: a sample dtype without a lossy mode."""
+    given = [k for k, v in (('target_bits', target_bits), ('target_ratio', target_ratio), ('target_psnr', target_psnr))
+             if v is not None]
+    if not given:
         if target_mode is not None:
-            raise ValueError('target_mode needs target_bits or target_ratio')
+            raise ValueError('target_mode needs target_bits, target_ratio or target_psnr')
         return None
-    if target_bits is not None and target_ratio is not None:
-        raise ValueError('give one of target_bits and target_ratio, not both')
-    if target_bits is not None:
-        _positive_finite('target_bits', target_bits)
-    else:
-        _positive_finite('target_ratio', target_ratio)
+    if len(given) > 1:
+        raise ValueError(f'give one of target_bits, target_ratio and target_psnr, not {" and ".join(given)}')
+    _positive_finite(given[0], {'target_bits': target_bits, 'target_ratio': target_ratio,
+                                'target_psnr': target_psnr}[given[0]])
     if isinstance(max_error, bool) or max_error != 0 or abs_error is not None or rel_error is not None:
-        raise ValueError('target_bits / target_ratio choose the bound: not with max_error, abs_error or rel_error')
-    if method != 'rice':
+        raise ValueError(f'{given[0]} chooses the bound: not with max_error, abs_error or rel_error')
+    if target_psnr is None and method != 'rice':
         raise ValueError("target_bits / target_ratio need method='rice' (only Rice bundles are sized on the device)")
     try:
         name = near._BY_NAME_INV[near.torch_dtype(dtype)]
     except (TypeError, KeyError):
         name = None
     if name not in MODES:
-        raise TypeError(f'no rate control for {dtype} samples (float32: abs / rel; uint8, uint16, int8, int16: near)')
+        raise TypeError(f'no rate or quality control for {dtype} samples (float32: abs / rel; uint8, uint16, int8, int16: near)')
     every = tuple(m for ms in MODES.values() for m in ms)
     if target_mode is None:
         return MODES[name][0]
@@ -119,12 +122,20 @@ def bound_of(mode, rung):
 
 
 class Unreachable(ValueError):
-    """No rung of the ladder fits the budget; ``coarsest`` is the size of the coarsest one."""
+    """No rung of the ladder fits the budget; ``coarsest`` is the size of the coarsest one.  From
+    :func:`search_quality`: no rung reaches the quality ``target``; ``finest`` is the finest one's."""
 
     def __init__(self, coarsest, budget):
         super().__init__(f'the budget of {budget} bytes cannot be met: the coarsest rung needs {coarsest} bytes '
                          f'(bound_bytes)')
         self.coarsest, self.budget = coarsest, budget
+
+    @classmethod
+    def quality(cls, finest, target):
+        e = cls(None, None)
+        e.args = (f'the quality target of {target} cannot be met: the finest rung reaches {finest}',)
+        e.finest, e.target = finest, target
+        return e
 
 
 def search(size, L, budget):
@@ -156,3 +167,37 @@ def search(size, L, budget):
         else:
             lo = mid
     return hi, probes
+
+
+def search_quality(quality, L, target):
+    """``(rung, probes)``: the rung in ``0 .. L - 1`` (0 the finest) to code for a quality of at least
+    ``target``, with ``quality(r)`` the figure of rung ``r`` (a PSNR in dB) and ``probes`` the
+    ``[(r, quality(r))]`` asked, in order.
+
+    1. ``quality(L - 1) >= target``: rung ``L - 1``.
+    2. else ``quality(0) < target``: :class:`Unreachable` (``finest`` holds rung 0's quality).
+    3. else bisect with ``lo = 0`` (meets the target) and ``hi = L - 1`` (fails): ``mid = (lo + hi) // 2``
+       goes to ``lo`` when it meets the target, else to ``hi``; stop at ``hi - lo == 1`` and take ``lo``.
+
+    Nothing is assumed about the quality being monotone in the rung: the rung returned meets the target,
+    its coarser neighbour does not (or does not exist), after at most ``2 + ceil(log2 L)`` probes."""
+    probes = []
+
+    def ask(r):
+        probes.append((r, float(quality(r))))
+        return probes[-1][1]
+    if ask(L - 1) >= target:
+        return L - 1, probes
+    if L == 1:
+        raise Unreachable.quality(probes[0][1], target)
+    finest = ask(0)
+    if not finest >= target:
+        raise Unreachable.quality(finest, target)
+    lo, hi = 0, L - 1
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if ask(mid) >= target:
+            lo = mid
+        else:
+            hi = mid
+    return lo, probes

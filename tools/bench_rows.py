@@ -668,6 +668,46 @@ def main():
             print(json.dumps(line), flush=True)
         del work, routes
 
+    # The comparing call (only with --rows compare): kmp_code with KMP_CODER_COMPARE on a 512^3
+    # float32 field and on 512 x 64^3 uint16 tiles against the torch composition the bound checks run for
+    # the same arrays (container._quant_max_error / near.d_max_abs_error without their restoring launch),
+    # alternated in one process, 9 samples of --reps calls; TBps_read counts both arrays once.
+    if 'compare' in want:
+        from kompressor_amd import metrics, near
+        gen = torch.Generator(device='cuda').manual_seed(0)
+        xf = torch.randn((512, 512, 512), device='cuda', generator=gen)
+        rf = xf + 2.0 ** -10 * torch.randn((512, 512, 512), device='cuda', generator=gen)
+        xu = vol.reshape(-1)
+        ru = (xu.view(torch.int16).to(torch.int32) & 0xffff).add_(torch.randint(-3, 4, xu.shape, device='cuda',
+                                                                                generator=gen)).clamp_(0, 65535).to(torch.uint16)
+        buf = metrics.d_compare(xf.reshape(-1), rf.reshape(-1))
+        slab = 1 << 24
+
+        def torch_f32():
+            worst = torch.zeros((), dtype=torch.float64, device='cuda')
+            a, b = xf.reshape(-1), rf.reshape(-1)
+            for s in range(0, a.numel(), slab):
+                worst = torch.maximum(worst, (b[s:s + slab].double() - a[s:s + slab].double()).abs_().max())
+            return worst
+        routes = {'f512_float32': {'compare': lambda: metrics.d_compare(xf.reshape(-1), rf.reshape(-1), buf),
+                                   'torch_max_abs': torch_f32},
+                  'c3_uint16': {'compare': lambda: metrics.d_compare(xu, ru, buf),
+                                'torch_max_abs': lambda: near.d_max_abs_error(ru, xu)}}  # with its read-back
+        nbytes = {'f512_float32': 2 * xf.numel() * 4, 'c3_uint16': 2 * xu.numel() * 2}
+        samples = {(t, d): [] for t in routes for d in routes[t]}
+        for _ in range(9):
+            for t in routes:
+                for d in routes[t]:
+                    samples[(t, d)].append(gpu_time(routes[t][d], args.reps))
+        med = {k: float(np.median(v)) for k, v in samples.items()}
+        for (t, d), v in samples.items():
+            line = {'row': f'compare:{t}:{d}', 'what': f'{nbytes[t]} bytes read, {kom._lib.COMPARE_BYTES} written',
+                    'TBps_read': round(nbytes[t] / med[(t, d)] / 1e12, 3), 'us': round(med[(t, d)] * 1e6, 1),
+                    'us_min': round(min(v) * 1e6, 1), 'us_max': round(max(v) * 1e6, 1), 'samples': len(v),
+                    'ratio_to_compare': round(med[(t, d)] / med[(t, 'compare')], 4)}
+            print(json.dumps(line), flush=True)
+        del xf, rf, ru, routes
+
     # geometry primitives (volume/utils.py) on the C3 tile batch
     if not want or 'primitives' in want:
         hp, _ = _nd.d_pad_highres(vol, 3)                       # [512, 65^3]

@@ -6,7 +6,9 @@ measures a build from before error-bounded coding.  ``--rel`` measures the relat
 (DESIGN.md §18): the field becomes ``10 ** (2 f)`` -- four decades -- times ``1 + noise / 15``, and the
 bounds are ``rel_error`` None, 1e-1, 1e-2, 1e-3.  ``--target`` measures rate control instead (DESIGN.md
 §19): ``compress(target_bits=4 / 8)`` against ``compress(abs_error=the chosen bound)``, the probes it
-made and the time of one probe."""
+made and the time of one probe.  ``--psnr`` measures quality targets:
+``compress(target_psnr=60 / 90)`` against ``compress(abs_error=the chosen bound)``, the probes, and the
+time of the quality pass every lossy ``compress`` now holds."""
 import json, os, sys, tempfile
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -63,6 +65,41 @@ if '--target' in sys.argv:
                           'probes': len(res['probes']), 'probe_rungs': [p[0] for p in res['probes']],
                           'target_total_ms': stat(rows['target']), 'explicit_total_ms': stat(rows['explicit']),
                           'one_probe_ms': stat(rows['probe'])}), flush=True)
+    os.remove(path)
+    sys.exit(0)
+if '--psnr' in sys.argv:
+    # quality targets: compress(target_psnr=dB) against compress(abs_error=chosen) on the same
+    # field, alternated over three timed rounds; the probes it made, and the device time of the quality
+    # pass the explicit call now holds (restore and compare in slabs, one read-back; synchronised)
+    import time
+    from kompressor_amd import quant, _lib
+    path = os.path.join(d, 'v.kmp')
+    for db in (60.0, 90.0):
+        rows = {'target': [], 'explicit': [], 'quality': []}
+        for rnd in range(4):
+            res = container.compress(path, xt, pred, levels=3, target_psnr=db)
+            tt = dict(container.last_timing)
+            target_bytes = open(path, 'rb').read()
+            ex = container.compress(path, xt, pred, levels=3, abs_error=res['abs_error'])
+            te = dict(container.last_timing)
+            assert open(path, 'rb').read() == target_bytes and res['psnr'] >= db and ex['psnr'] == res['psnr']
+            e = quant.exponent(res['abs_error'])
+            nq, exc = quant.d_quantise(xt, e)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            q = container._quality(container._restored_record(xt, nq, lambda s: quant.d_code(_lib.DECODE, nq.dtype, e, s), exc),
+                                   xt.dtype)
+            tq = time.perf_counter() - t0
+            assert q['psnr'] == res['psnr']
+            del nq
+            if rnd:
+                rows['target'].append(tt['total']); rows['explicit'].append(te['total']); rows['quality'].append(tq)
+        stat = lambda xs: [round(1e3 * f(xs), 2) for f in (lambda v: float(np.median(v)), min, max)]
+        print(json.dumps({'target_psnr': db, 'abs_error': res['abs_error'], 'psnr': res['psnr'],
+                          'bits_per_sample': round(res['bits_per_sample'], 4), 'bytes': res['bytes'],
+                          'probes': len(res['probes']), 'probe_rungs': [p[0] for p in res['probes']],
+                          'target_total_ms': stat(rows['target']), 'explicit_total_ms': stat(rows['explicit']),
+                          'quality_pass_ms': stat(rows['quality'])}), flush=True)
     os.remove(path)
     sys.exit(0)
 for rnd in range(4):
