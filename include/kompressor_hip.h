@@ -106,7 +106,40 @@ typedef enum {
      (whatever the count), KMP_DECODE, a mode field other than 0 / 1, differing or unsupported dtypes, a
      misaligned ``out``, 16-bit samples with n >= 2^32 (the u64 sum could overflow), or this code on
      any other entry point.  kmp_last_launch() names it "compare". */
-  KMP_CODER_COMPARE = 10
+  KMP_CODER_COMPARE = 10,
+  /* Hold-fill of a quantiser's marked output (kmp_code alone, KMP_ENCODE alone).  ``x`` is
+     an int16 / int32 array (``x_dtype`` KMP_I16 / KMP_I32) in which the type's minimum MARKS an element,
+     as the quantisers' ENCODE writes it; ``out`` is the array of the same dtype and count in which every
+     marked element holds the last unmarked value before it in index order, the marked elements before
+     the first unmarked one hold that first value, an array with no unmarked element is all 0, and
+     every unmarked element is unchanged.  ``out`` may be ``x`` itself (a lane reads the 8 elements it
+     writes before it writes them, and nothing else reads them); any other overlap of the two arrays is
+     refused.  ``pred`` is the scratch: a device buffer of KMP_FILL_BYTES, 8-byte aligned, non-NULL whatever
+     the count; its contents on entry do not matter and ``pred_dtype`` is not read.  Workgroup g of
+     ceil(T / P), T = ceil(n / KMP_FILL_TILE), P = ceil(T / KMP_FILL_GROUPS), owns the elements
+     [g P KMP_FILL_TILE, (g + 1) P KMP_FILL_TILE): a function of n alone.  Both arrays 16-byte
+     aligned: 16-byte non-temporal accesses; any other alignment (the dtype's at least): element accesses.
+     Three launches on ``stream``, no atomics; the same buffers give the same bytes on every call.
+     KMP_ERR_ARG, with nothing launched: KMP_DECODE, another x_dtype, a non-zero field above the low byte, a
+     NULL or misaligned ``pred``, arrays not aligned to their dtype, partly overlapping arrays, or this
+     code on any other entry point.  n == 0 is KMP_OK and touches nothing.  kmp_last_launch() names
+     it "fill". */
+  KMP_CODER_FILL = 11,
+  /* Patch of a float32 array from a run table (kmp_code alone, KMP_DECODE alone).  ``x`` is
+     the table on the device: n = R records of four uint32 -- the low and the high word of ``start``,
+     ``length``, ``bits`` --, 16-byte aligned, ``x_dtype`` KMP_U32; ``out`` is the float32 array, 4-byte
+     aligned, patched in place: ``bits`` is written over the elements [start, start + length) of every
+     record and nothing else is touched.  ``pred`` must be NULL.  The bounds are the CALLER's duty: the
+     kernel does not know the array's size, so every [start, start + length) must lie inside it (the
+     Python layer checks the extents on the device, with one read-back, before the launch); records
+     must not overlap.  A record of any length is served, but a wave owns 64 consecutive records and
+     walks the long ones among them (more than 8 elements) one after the other: cut long runs into records
+     of at most KMP_RUNS_PIECE elements when the table is built, so that a long run spreads over one wave per
+     64 records.  KMP_ERR_ARG, with nothing launched:
+     KMP_ENCODE, another x_dtype, a non-zero field above the low byte, a non-NULL ``pred``, a misaligned
+     table or array, or this code on any other entry point.  R == 0 is KMP_OK.  One launch;
+     kmp_last_launch() names it "runs". */
+  KMP_CODER_RUNS = 12
 } kmp_coder;
 #define KMP_CODER_NEAR(code, max_error) ((code) | ((max_error) << 8))
 #define KMP_CODER_QUANT(code, exp) ((code) | (((exp) + 127) << 8))
@@ -114,6 +147,10 @@ typedef enum {
 #define KMP_CODER_COMPARE_MODE(cont) (KMP_CODER_COMPARE | ((cont) << 8))
 #define KMP_COMPARE_GROUPS 1024
 #define KMP_COMPARE_BYTES (64 * (1 + KMP_COMPARE_GROUPS))
+#define KMP_FILL_TILE 2048
+#define KMP_FILL_GROUPS 1024
+#define KMP_FILL_BYTES (16 * KMP_FILL_GROUPS)
+#define KMP_RUNS_PIECE 256
 typedef enum { KMP_ENCODE = 0, KMP_DECODE = 1 } kmp_direction;
 
 typedef enum {
@@ -324,7 +361,10 @@ int kmp_tiles(int32_t nsp, int32_t dtype, int32_t direction, const void* src, co
    Quantisers (KMP_CODER_QUANT and KMP_CODER_PREC, see kmp_coder): ``pred`` is NULL; float32 ->
    int16 / int32 (ENCODE), int16 / int32 -> float32 (DECODE).
    KMP_CODER_COMPARE (see kmp_coder): ``x`` the original, ``pred`` the restored array of the same dtype,
-   ``out`` the KMP_COMPARE_BYTES of the error statistics; ENCODE alone. */
+   ``out`` the KMP_COMPARE_BYTES of the error statistics; ENCODE alone.
+   KMP_CODER_FILL (see kmp_coder): ``x`` the marked int16 / int32 array, ``out`` the filled one, ``pred`` the
+   KMP_FILL_BYTES of scratch; ENCODE alone.  KMP_CODER_RUNS (see kmp_coder): ``x`` the run table (n records),
+   ``out`` the float32 array patched in place, ``pred`` NULL; DECODE alone. */
 int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* pred, int32_t x_dtype,
              const void* x, int64_t n, void* out, kmp_stream_t stream);
 

@@ -69,6 +69,23 @@ def coder_compare(cont=False):
     return CODER_COMPARE | (int(bool(cont)) << 8)
 
 
+# masked float32 fields (kmp_code alone).  CODER_FILL (ENCODE alone): the hold-fill of a marked
+# int16 / int32 array, ``pred`` the FILL_BYTES of scratch; workgroup g owns the elements from g * fill_span(n).
+# CODER_RUNS (DECODE alone): a float32 array patched from a table of (start low, start high, length, bits)
+# records, long runs cut into pieces of RUNS_PIECE when the table is built
+CODER_FILL, CODER_RUNS = 11, 12
+FILL_TILE = 2048
+FILL_GROUPS = 1024
+FILL_BYTES = 16 * FILL_GROUPS
+RUNS_PIECE = 256
+
+
+def fill_span(n):
+    """The elements one workgroup of the fill owns in an array of ``n``: a function of ``n`` alone."""
+    tiles = -(-int(n) // FILL_TILE)
+    return -(-tiles // FILL_GROUPS) * FILL_TILE
+
+
 def coder_code(coder):
     return int(coder) & 0xff
 

@@ -27,7 +27,8 @@ and a failing ``decompress`` name the damaged ones.  ``bundle_bytes`` and ``crc3
 alone either way, and a reader that does not know the key reads the file as before.
 Version 4 is a near-lossless file (``'max_error'``), version 5 an error-bounded float32 file
 (``'quant'``, and its exception arrays behind the maps), version 6 a relative-error float32 file
-(``'prec'``); see ``VERSION_NEAR`` / ``VERSION_QUANT`` / ``VERSION_PREC`` below.
+(``'prec'``), version 7 either of the two with its exceptions stored as runs (``'exception_runs'``); see
+``VERSION_NEAR`` / ``VERSION_QUANT`` / ``VERSION_PREC`` / ``VERSION_RUNS`` below.
 
 The host side of the file path (round 4): the bundle's CRC-32 (zlib's, the value the file stores)
 is computed on the device (``kmp_crc32``) -- over the bundle the encode just wrote, its length read
@@ -71,6 +72,14 @@ VERSION_QUANT = 5
 # ``quant.quantise_rel`` and the metadata's 'prec' = {'bits', 'dtype', 'exceptions': E} records the
 # mantissa bits kept in place of 'quant'.  The exception arrays are version 5's.  Older builds refuse it.
 VERSION_PREC = 6
+# 7: a version-5 or version-6 file whose exceptions are stored as runs (``exceptions='runs'``
+# with E > 0): the metadata is that version's -- exactly one well-formed 'quant' or 'prec' -- plus
+# 'exception_runs' = R, 1 <= R <= E; the integers under the exceptions are hold-filled, and the bundle ends
+# with FOUR uint32 arrays of R entries (``quant.d_runs``): the low and high words of the gaps between
+# consecutive run starts, the lengths, the differences of consecutive runs' bits modulo 2^32.  Older builds
+# refuse version 7; with E == 0 the file is the version-5 / 6 one, byte for byte.
+VERSION_RUNS = 7
+_EXCEPTIONS = ('list', 'runs')
 _QUANT_DTYPES ={'int16': torch.int16, 'int32': torch.int32}
 _QUANT_SLAB = 1 << 24  # elements per slab of the bound's check
 _HEAD = struct.Struct('<4sHHQ')
@@ -155,6 +164,31 @@ def _check_prec(meta, version, path):
     if meta.get('sample_dtype') != 'float32':
         raise ValueError(f'{path}: a version-{VERSION_PREC} (relative-error) file of {meta.get("sample_dtype")!r} '
                          f'samples (float32 only)')
+
+
+def _check_runs(meta, version, path):
+    """The version whose rules the rest of the metadata follows.  A version-7 file carries exactly one of
+    'quant' / 'prec' (checked as version 5 / 6 by the caller) and a well-formed 'exception_runs' R with
+    1 <= R <= E; no other version has an 'exception_runs'."""
+    if version != VERSION_RUNS:
+        if 'exception_runs' in meta:
+            raise ValueError(f'{path}: a version-{version} file with an exception_runs entry (files with exception '
+                             f'runs are version {VERSION_RUNS})')
+        return version
+    if ('quant' in meta) == ('prec' in meta):
+        raise ValueError(f'{path}: a version-{VERSION_RUNS} (exception runs) file needs exactly one of quant and prec')
+    base = VERSION_QUANT if 'quant' in meta else VERSION_PREC
+    (_check_quant if base == VERSION_QUANT else _check_prec)(meta, base, path)
+    R, E = meta.get('exception_runs'), meta['quant' if base == VERSION_QUANT else 'prec']['exceptions']
+    if isinstance(R, bool) or not isinstance(R, int) or not 1 <= R <= E:
+        raise ValueError(f'{path}: a version-{VERSION_RUNS} (exception runs) file with a bad exception_runs entry '
+                         f'{R!r} ({E} exceptions)')
+    return base
+
+
+def _runs(meta):
+    """R of a file whose header ``_read_head`` accepted and that stores its exceptions as runs, else 0."""
+    return int(meta.get('exception_runs') or 0)
 
 
 def _quant(meta):
@@ -367,7 +401,8 @@ def _read_head(f, path):
     if len(head) < _HEAD.size:
         raise ValueError(f'{path}: not a kompressor_amd file (too short)')
     magic, version, _, mlen = _HEAD.unpack(head)
-    if magic != MAGIC or version not in (1, 2, VERSION, VERSION_NEAR, VERSION_QUANT, VERSION_PREC) or mlen > (1 << 26):
+    if magic != MAGIC or version not in (1, 2, VERSION, VERSION_NEAR, VERSION_QUANT, VERSION_PREC, VERSION_RUNS) or \
+            mlen > (1 << 26):
         raise ValueError(f'{path}: not a kompressor_amd file (magic {magic!r}, version {version})')
     try:
         meta = json.loads(f.read(mlen).decode())
@@ -375,9 +410,10 @@ def _read_head(f, path):
     except (ValueError, KeyError, TypeError) as e:
         raise ValueError(f'{path}: corrupt metadata ({e})') from None
     _check_sample_dtype(meta, path)
-    _check_max_error(meta, version, path)
-    _check_quant(meta, version, path)
-    _check_prec(meta, version, path)
+    base = _check_runs(meta, version, path)  # a version-7 file follows version 5's or 6's rules
+    _check_max_error(meta, base, path)
+    _check_quant(meta, base, path)
+    _check_prec(meta, base, path)
     if version == 1 and meta.get('method') != 'planes':
         # version-1 'rice' payloads were the per-array KMPR format, replaced by the v2 bundle;
         # version-1 'planes' payloads are unchanged and still read
@@ -530,8 +566,19 @@ def _check_bounds(highres, max_error, abs_error, rel_error):
     return exp, bits
 
 
+def _check_exceptions(exceptions, abs_error, rel_error, mode=None):
+    """The ``exceptions`` keyword of a ``compress`` / ``compressed_size`` call, checked on the host alone:
+    whether the exceptions are stored as runs.  ValueError for a value other than 'list' / 'runs', and for
+    'runs' without ``abs_error``, ``rel_error`` or a float32 target (only those files have exceptions)."""
+    if not isinstance(exceptions, str) or exceptions not in _EXCEPTIONS:
+        raise ValueError(f"exceptions must be 'list' or 'runs', got {exceptions!r}")
+    if exceptions == 'runs' and abs_error is None and rel_error is None and mode not in ('abs', 'rel'):
+        raise ValueError("exceptions='runs' needs abs_error, rel_error or a float32 target: no other file has exceptions")
+    return exceptions == 'runs'
+
+
 def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None,
-             rel_error=None, target_bits=None, target_ratio=None, target_mode=None, target_psnr=None):
+             rel_error=None, target_bits=None, target_ratio=None, target_mode=None, target_psnr=None, exceptions='list'):
     """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
     :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int8 / int16
     modular on the sign-mapped samples, int32 raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
@@ -575,24 +622,31 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
     order asked).  A target above the finest rung's PSNR raises ValueError and writes nothing.
     Quality figures: every lossy result also holds ``'mse'``, ``'psnr'`` and ``'value_range'``, measured by
     ``kom.metrics`` on exactly what :func:`decompress` returns (NaNs and infinities, which come back bit for
-    bit, are not compared); a lossless one holds ``'mse': 0.0`` and ``'psnr': inf``."""
+    bit, are not compared); a lossless one holds ``'mse': 0.0`` and ``'psnr': inf``.
+    ``exceptions='runs'`` (with ``abs_error``, ``rel_error`` or a float32 target): for masked fields --
+    the values that cannot be quantised are stored as runs of consecutive indices with equal bits
+    (``quant.runs``) instead of one index and 32 bits each, and the integers under them are hold-filled
+    (``quant.fill``) so that a hole costs the pyramid next to nothing.  What :func:`decompress` returns is bit
+    for bit what the ``'list'`` file returns.  With exceptions the file is version 7; without any it is the
+    ``'list'`` file byte for byte.  The result also holds ``'exception_runs'``."""
     mode = rate.check_target(near._input_dtype(highres), target_bits, target_ratio, target_mode, method, max_error,
                              abs_error, rel_error, target_psnr)  # before the device is touched
     exp, bits = _check_bounds(highres, max_error, abs_error, rel_error)  # before the device is touched
+    runs = _check_exceptions(exceptions, abs_error, rel_error, mode)  # before the device is touched
     t0 = time.perf_counter()
     packing._check_method(method)
     _check_tile_crc_method(tile_crc, method)
     h, _ = dev.to_device(highres)
     if target_psnr is not None:
-        return _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, float(target_psnr), t0)
+        return _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, float(target_psnr), t0, runs)
     if mode is not None:
-        return _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0)
+        return _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0, runs)
     if max_error:
         return _compress_near(path, h, predictor, levels, method, tile_crc, int(max_error), t0)
     if exp is not None:
-        return _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0)
+        return _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0, runs)
     if bits is not None:
-        return _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0)
+        return _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0, runs)
     return _compress_lossless(path, h, predictor, levels, method, tile_crc, t0)
 
 
@@ -699,34 +753,43 @@ def _quant_max_error(h, n, exp, exceptions):
     return float(worst.item())
 
 
-def _parts_quantised(h, predictor, levels, method, key, param, value, quantise):
+def _parts_quantised(h, predictor, levels, method, key, param, value, quantise, runs=False):
     """The quantiser (``quantise(h, value)``), the lossless pyramid of its integers ``'n'``, the
-    exceptions ``'exc'`` (``'E'`` of them) behind the maps, the metadata's ``key`` entry."""
+    exceptions ``'exc'`` (``'E'`` of them) behind the maps, the metadata's ``key`` entry.  ``runs``: the
+    integers under the exceptions are hold-filled and the exceptions ride as ``'R'`` runs."""
     ndim, padding = predictor.ndim, predictor.padding
-    n, exc = quantise(h, value)
-    x, arrays, meta_levels, levels = _lossless_levels(n, predictor, levels)
+    n, exc = quantise(h, value, marks=runs)  # runs: the marks ENCODE wrote stay in n
     E = 0 if exc is None else int(exc[0].numel())
-    if E:  # the exceptions ride behind the maps: gap words (low, high), then the bits
+    if E and runs:  # n is this call's own tensor: filled in place (kmp_code allows out == x for the fill)
+        n = quant.d_fill(n, out=n)
+    x, arrays, meta_levels, levels = _lossless_levels(n, predictor, levels)
+    R = 0
+    if E and runs:  # the runs ride behind the maps: start gap words (low, high), lengths, bit deltas
+        stored = quant.d_runs(*exc)
+        arrays, R = [*arrays, *stored], int(stored[0].numel())
+    elif E:  # the exceptions ride behind the maps: gap words (low, high), then the bits
         arrays = [*arrays, *quant.d_gaps(exc[0]), exc[1]]
     meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'method': method,
             'sample_dtype': 'float32', 'levels': meta_levels, 'lowres_shape': list(x.shape),
             'predictor': _predictor_meta(predictor, padding, ndim, x.dtype),
             key: {param: value, 'dtype': _NP_NAME[n.dtype], 'exceptions': E}}
-    return {'x': x, 'arrays': arrays, 'meta': meta, 'levels': levels, 'n': n, 'exc': exc, 'E': E}
+    if R:
+        meta['exception_runs'] = R
+    return {'x': x, 'arrays': arrays, 'meta': meta, 'levels': levels, 'n': n, 'exc': exc, 'E': E, 'R': R}
 
 
-def _parts_quant(h, predictor, levels, method, exp):
-    return _parts_quantised(h, predictor, levels, method, 'quant', 'exp', exp, quant.d_quantise)
+def _parts_quant(h, predictor, levels, method, exp, runs=False):
+    return _parts_quantised(h, predictor, levels, method, 'quant', 'exp', exp, quant.d_quantise, runs)
 
 
-def _parts_prec(h, predictor, levels, method, bits):
-    return _parts_quantised(h, predictor, levels, method, 'prec', 'bits', bits, quant.d_quantise_rel)
+def _parts_prec(h, predictor, levels, method, bits, runs=False):
+    return _parts_quantised(h, predictor, levels, method, 'prec', 'bits', bits, quant.d_quantise_rel, runs)
 
 
-def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0):
+def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0, runs=False):
     """:func:`compress` with ``abs_error``: the quantiser, the lossless pyramid of its integers, the
     bound's check, the version-5 file."""
-    p = _parts_quant(h, predictor, levels, method, exp)
+    p = _parts_quant(h, predictor, levels, method, exp, runs)
     n, E = p['n'], p['E']
     eps = quant.effective(abs_error)
     worst = _quant_max_error(h, n, exp, p['exc'])
@@ -734,11 +797,11 @@ def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp
         raise RuntimeError(f'error-bounded encode broke its bound: max |restored - highres| = {worst} > {eps} '
                            f'(abs_error = {abs_error}); nothing written to {path}')
     blob, total, crc, table = _bundle(p['x'], p['arrays'], (), method, tile_crc)
-    nbytes = _write(path, p['meta'], blob, total, crc, t0, table, VERSION_QUANT)
+    nbytes = _write(path, p['meta'], blob, total, crc, t0, table, VERSION_RUNS if p['R'] else VERSION_QUANT)
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
             'levels': p['levels'], 'abs_error': eps, 'abs_error_asked': float(abs_error), 'max_abs_error': worst,
-            'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype],
+            'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype], **({'exception_runs': p['R']} if runs else {}),
             **_quality(_restored_record(h, n, lambda s: quant.d_code(_lib_decode, n.dtype, exp, s), p['exc']), h.dtype)}
 
 
@@ -759,10 +822,10 @@ def _prec_max_error(h, n, bits, exceptions):
     return float(worst.item())
 
 
-def _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0):
+def _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0, runs=False):
     """:func:`compress` with ``rel_error``: the mantissa quantiser, the lossless pyramid of its integers,
     the guarantee's check, the version-6 file."""
-    p = _parts_prec(h, predictor, levels, method, bits)
+    p = _parts_prec(h, predictor, levels, method, bits, runs)
     n, E = p['n'], p['E']
     eps = quant.effective_rel(rel_error)
     worst = _prec_max_error(h, n, bits, p['exc'])
@@ -770,26 +833,28 @@ def _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits
         raise RuntimeError(f'relative-error encode broke its bound: max |restored - highres| / max(|highres|, 2^-126) '
                            f'= {worst} > {eps} (rel_error = {rel_error}); nothing written to {path}')
     blob, total, crc, table = _bundle(p['x'], p['arrays'], (), method, tile_crc)
-    nbytes = _write(path, p['meta'], blob, total, crc, t0, table, VERSION_PREC)
+    nbytes = _write(path, p['meta'], blob, total, crc, t0, table, VERSION_RUNS if p['R'] else VERSION_PREC)
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
             'levels': p['levels'], 'rel_error': eps, 'rel_error_asked': float(rel_error), 'max_rel_error': worst,
-            'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype],
+            'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype], **({'exception_runs': p['R']} if runs else {}),
             **_quality(_restored_record(h, n, lambda s: quant.d_code_rel(_lib_decode, n.dtype, bits, s), p['exc']),
                        h.dtype)}
 
 
-def _sized(h, predictor, levels, tile_crc, max_error=0, abs_error=None, rel_error=None):
+def _sized(h, predictor, levels, tile_crc, max_error=0, abs_error=None, rel_error=None, runs=False):
     """:func:`compressed_size` of the device tensor ``h`` with checked arguments."""
     if max_error:
         p = _parts_near(h, predictor, levels, 'rice', int(max_error))
         own = {'max_error': int(max_error)}
     elif abs_error is not None:
-        p = _parts_quant(h, predictor, levels, 'rice', quant.exponent(abs_error))
-        own = {'abs_error': quant.effective(abs_error), 'exceptions': p['E'], 'quant_dtype': _NP_NAME[p['n'].dtype]}
+        p = _parts_quant(h, predictor, levels, 'rice', quant.exponent(abs_error), runs)
+        own = {'abs_error': quant.effective(abs_error), 'exceptions': p['E'], 'quant_dtype': _NP_NAME[p['n'].dtype],
+               **({'exception_runs': p['R']} if runs else {})}
     elif rel_error is not None:
-        p = _parts_prec(h, predictor, levels, 'rice', quant.mantissa_bits(rel_error))
-        own = {'rel_error': quant.effective_rel(rel_error), 'exceptions': p['E'], 'quant_dtype': _NP_NAME[p['n'].dtype]}
+        p = _parts_prec(h, predictor, levels, 'rice', quant.mantissa_bits(rel_error), runs)
+        own = {'rel_error': quant.effective_rel(rel_error), 'exceptions': p['E'], 'quant_dtype': _NP_NAME[p['n'].dtype],
+               **({'exception_runs': p['R']} if runs else {})}
     else:
         p = _parts_lossless(h, predictor, levels, 'rice')
         own = {'max_error': 0}
@@ -801,26 +866,28 @@ def _sized(h, predictor, levels, tile_crc, max_error=0, abs_error=None, rel_erro
 
 
 def compressed_size(highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None,
-                    rel_error=None):
+                    rel_error=None, exceptions='list'):
     """The size of the file :func:`compress` would write for the same arguments, without writing it:
     the same argument checks, the same quantiser and pyramid (or closed loop), then the measuring
     launches of the Rice bundle (``packing.bundle_size``: the arrays are read once, no bundle is
     allocated, 8 bytes come back).  Returns ``{'bound_bytes', 'bundle_bytes', 'raw_bytes', 'levels'}`` and
     the mode's own entries (``'max_error'``; ``'abs_error'`` or ``'rel_error'`` -- the effective bound --
-    with ``'exceptions'`` and ``'quant_dtype'``).  ``bundle_bytes`` is exact.  ``bound_bytes`` is the
+    with ``'exceptions'`` and ``'quant_dtype'``, and ``'exception_runs'`` under ``exceptions='runs'``, the
+    keyword of :func:`compress`).  ``bundle_bytes`` is exact.  ``bound_bytes`` is the
     file's length with the metadata's ``crc32`` at its widest, 4294967295 (the CRC is stored as a
     decimal and is not known before the bytes exist): the file written is never larger and at most 16
     bytes smaller.  The bound itself is not checked here (:func:`compress` checks it before it writes).
     ``method='planes'`` raises ValueError: only Rice bundles are sized on the device."""
     _check_bounds(highres, max_error, abs_error, rel_error)  # before the device is touched
+    runs = _check_exceptions(exceptions, abs_error, rel_error)
     packing._check_method(method)
     if method != 'rice':
         raise ValueError("compressed_size needs method='rice' (only Rice bundles are sized on the device)")
     h, _ = dev.to_device(highres)
-    return _sized(h, predictor, levels, tile_crc, max_error, abs_error, rel_error)
+    return _sized(h, predictor, levels, tile_crc, max_error, abs_error, rel_error, runs)
 
 
-def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0):
+def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0, runs=False):
     """:func:`compress` with ``target_bits`` / ``target_ratio``: the ladder of ``mode``, the search over
     it with :func:`compressed_size` as the size of a rung, then the chosen rung written by the
     explicit-bound path (which still checks its bound before it writes)."""
@@ -837,7 +904,7 @@ def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, ta
 
     def size(r):
         key, value = rate.bound_of(mode, ladder[r])
-        return _sized(h, predictor, levels, tile_crc, **{key: value})['bound_bytes']
+        return _sized(h, predictor, levels, tile_crc, runs=runs, **{key: value})['bound_bytes']
     try:
         r, probes = rate.search(size, len(ladder), budget)
     except rate.Unreachable as e:
@@ -845,9 +912,9 @@ def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, ta
                          f'ladder has bound_bytes = {e.coarsest}; nothing written') from None
     key, value = rate.bound_of(mode, ladder[r])
     if mode == 'abs':
-        out = _compress_quant(path, h, predictor, levels, 'rice', tile_crc, value, ladder[r], t0)
+        out = _compress_quant(path, h, predictor, levels, 'rice', tile_crc, value, ladder[r], t0, runs)
     elif mode == 'rel':
-        out = _compress_prec(path, h, predictor, levels, 'rice', tile_crc, value, ladder[r], t0)
+        out = _compress_prec(path, h, predictor, levels, 'rice', tile_crc, value, ladder[r], t0, runs)
     elif value:
         out = _compress_near(path, h, predictor, levels, 'rice', tile_crc, value, t0)
     else:  # rung 0 of the 'near' ladder is the lossless file
@@ -855,7 +922,7 @@ def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, ta
     return dict(out, target_bytes=budget, bound_bytes=dict(probes)[r], probes=[(ladder[q], b) for q, b in probes])
 
 
-def _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, target, t0):
+def _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, target, t0, runs=False):
     """:func:`compress` with ``target_psnr``: the ladder of ``mode``, ``rate.search_quality`` over it with the
     PSNR of a rung measured on the device -- float32: the quantiser, then restore and compare in slabs;
     integer samples: the closed loop's restored array against the input -- then the chosen rung written
@@ -889,9 +956,9 @@ def _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, target, t
                          f'reaches {e.finest} dB; nothing written') from None
     key, value = rate.bound_of(mode, ladder[r])
     if mode == 'abs':
-        out = _compress_quant(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0)
+        out = _compress_quant(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0, runs)
     elif mode == 'rel':
-        out = _compress_prec(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0)
+        out = _compress_prec(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0, runs)
     elif value:
         out = _compress_near(path, h, predictor, levels, method, tile_crc, value, t0)
     else:  # rung 0 of the 'near' ladder is the lossless file
@@ -926,6 +993,18 @@ def _quant_exceptions(path, arrays, E, numel):
     if int(idx.min().item()) < 0 or int(idx.max().item()) >= numel:
         raise ValueError(f'{path}: an exception index lies outside the array (corrupt file)')
     return idx, bits
+
+
+def _quant_runs(path, arrays, R, numel):
+    """The KMP_CODER_RUNS table from a version-7 bundle's last four arrays, checked (R entries each, uint32,
+    every run of at least one element and inside the array, the runs ascending and disjoint: one read-back)
+    before anything is written by it."""
+    if any(a.dtype != torch.uint32 or tuple(a.shape) != (R,) for a in arrays):
+        raise ValueError(f'{path}: the exception run arrays do not match the metadata ({R} runs)')
+    try:
+        return quant.d_run_table(*arrays, numel)
+    except ValueError as e:
+        raise ValueError(f'{path}: {e} (corrupt file)') from None
 
 
 def _decode_predictor(path, meta, predictor, dtype):
@@ -963,10 +1042,11 @@ def decompress(path, predictor=None, as_numpy=True):
     if q is not None:
         if lowres.dtype != q[1]:
             raise ValueError(f'{path}: the bundle holds {lowres.dtype} samples, the metadata says {q[1]}')
-        if q[2]:  # the three exception arrays behind the maps
-            if len(arrays) < 3:
+        if q[2]:  # the three exception arrays behind the maps, or the four run arrays
+            k = 4 if _runs(meta) else 3
+            if len(arrays) < k:
                 raise ValueError(f'{path}: the exception arrays are missing from the bundle')
-            arrays, extra = arrays[:-3], arrays[-3:]
+            arrays, extra = arrays[:-k], arrays[-k:]
     pred = _decode_predictor(path, meta, predictor, lowres.dtype)
     ndim, padding = meta['ndim'], meta['padding']
     nmaps = _nd.NMAPS[ndim]
@@ -986,7 +1066,10 @@ def decompress(path, predictor=None, as_numpy=True):
         else:
             out = _nd.decode(pred, dec_fn, x, (maps, dims), padding, ndim)
         x = out
-    if q is not None:  # one dequantising launch, then the exceptions' bits
+    if q is not None and extra is not None and _runs(meta):  # one dequantising launch, then one RUNS launch
+        table = _quant_runs(path, extra, _runs(meta), x.numel())
+        x = quant.d_patch_runs(q[3](x, q[0], None), table)
+    elif q is not None:  # one dequantising launch, then the exceptions' bits
         x = q[3](x, q[0], None if extra is None else _quant_exceptions(path, extra, q[2], x.numel()))
     elif meta.get('sample_dtype') == 'float32':
         x = x.view(torch.float32)
@@ -1048,7 +1131,7 @@ def info(path):
             out['max_error'] = _max_error(meta)
         if _quant(meta) is not None:  # only an error-bounded or a relative-error file reports its bound
             param, qdt, E, _ = _quant(meta)
-            out.update(quant_dtype=_NP_NAME[qdt], exceptions=E,
+            out.update(quant_dtype=_NP_NAME[qdt], exceptions=E, **({'exception_runs': _runs(meta)} if _runs(meta) else {}),
                        **({'rel_error': 2.0 ** -(param + 1)} if 'prec' in meta else {'abs_error': 2.0 ** (param - 1)}))
         trailer = _tile_crc_trailer(meta, n, size - (_HEAD.size + mlen), path)
         if trailer is not None:  # only a file that has a table reports one
@@ -1068,9 +1151,13 @@ def _meta_tile_counts(meta):
 
 def _exception_arrays(meta):
     """The lengths of the arrays behind the maps: three of E entries in an error-bounded or a
-    relative-error file that has exceptions, none in any other file."""
+    relative-error file that has exceptions -- four of R entries when they are stored as runs --, none
+    in any other file."""
     q = meta.get('quant') or meta.get('prec')
     E = int(q['exceptions']) if isinstance(q, dict) else 0
+    R = meta.get('exception_runs')
+    if E > 0 and isinstance(R, int) and not isinstance(R, bool) and R > 0:
+        return [R] * 4
     return [E] * 3 if E > 0 else []
 
 
@@ -1279,7 +1366,8 @@ def plan_region(meta, planes=None, batch=None, rows=None, cols=None, level=0):
     arrays = [entry(lo_shape, lowres_axes[:ncrop], [e - s for s, e in lowres_axes[:ncrop]], [0] * ncrop)] + \
         skipped + map_entries
     assert len(arrays) == 1 + nmaps * nlev
-    # an error-bounded file's exception arrays (gap words, bits) are read whole, whatever the selection
+    # an error-bounded file's exception arrays (gap words, bits; or the four run arrays) are read whole, whatever
+    # the selection
     arrays += [{'shape': (E,), 'sel': (0, E), 'local_shape': (E,), 'local_at': 0, 'sel_rows': (0, E), 'local_row_at': 0,
                 'ranges': [(0, E, 0)]} for E in _exception_arrays(meta)]
     for i, e in enumerate(arrays):
@@ -1384,8 +1472,9 @@ def _region_windows(fd, path, base, nbytes, rplan, plan, crc_table=None):
 def _region_restore(meta, plan, x, extra):
     """The float32 box of an error-bounded file from its integer box ``x`` (contiguous): one
     dequantising launch, then the bits of the exceptions that fall in it -- at level ``k`` those whose
-    spatial coordinates are all multiples of ``2**k``.  ``extra``: the gap words and the bits, or None.
-    Every index is masked to the box before it addresses anything, so damaged arrays cannot write
+    spatial coordinates are all multiples of ``2**k``.  ``extra``: the gap words and the bits, or the four run
+    arrays, or None.  Runs are clipped to the flat interval the box spans and only what is left of them is
+    expanded to indices.  Every index is masked to the box before it addresses anything, so damaged arrays cannot write
     outside the result (the caller's tile checks report them)."""
     param, _, _, d_restore = _quant(meta)
     out = d_restore(x, param, None)
@@ -1393,8 +1482,24 @@ def _region_restore(meta, plan, x, extra):
         return out
     ndim, k = int(meta['ndim']), plan['level']
     shape0 = _meta_shapes(meta)[0][0]
-    idx, bits = quant.d_indices(extra[0], extra[1]), extra[2]
     spans = [plan['batch'], *plan['box'], *[(0, s) for s in shape0[1 + ndim:]]]
+    if len(extra) == 4:
+        # the flat interval of level 0 between the box's first and last element
+        first = last = 0
+        for a, (s, (lo, hi)) in enumerate(zip(shape0, spans)):
+            sh = k if 1 <= a <= ndim else 0
+            first, last = first * s + (lo << sh), last * s + min(((hi - 1) << sh), s - 1)
+        starts, lengths, rbits = quant.d_run_starts(*extra)
+        try:  # inside the array, ascending, disjoint -- as decompress checks them -- before any sum is formed
+            quant.d_check_runs(starts, lengths, dev.prod(shape0))
+        except ValueError as e:
+            raise ValueError(f'{e} (corrupt file)') from None
+        ends = torch.clamp(starts + lengths, max=last + 1)
+        starts = torch.clamp(starts, min=first)
+        inside = ends > starts
+        idx, bits = quant.d_expand(starts[inside], (ends - starts)[inside], rbits[inside])
+    else:
+        idx, bits = quant.d_indices(extra[0], extra[1]), extra[2]
     keep = (idx >= 0) & (idx < dev.prod(shape0))
     flat, rem, stride = torch.zeros_like(idx), idx, 1
     for a in reversed(range(len(shape0))):
@@ -1509,7 +1614,8 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
         q = _quant(meta)
         if q is not None and dtype != q[1]:
             raise ValueError(f'{path}: the bundle holds {dtype} samples, the metadata says {q[1]}')
-        if q is not None and q[2] and any(dev.CODE_TO_TORCH[c] != torch.uint32 for c in rplan['codes'][-3:]):
+        nexc = len(_exception_arrays(meta))
+        if q is not None and q[2] and any(dev.CODE_TO_TORCH[c] != torch.uint32 for c in rplan['codes'][-nexc:]):
             raise ValueError(f'{path}: the exception arrays of the bundle are not uint32')
         pred = _decode_predictor(path, meta, predictor, dtype)
         buf, used, jobs, payload_bytes, crc_offs = _region_windows(fd, path, base, nbytes, rplan, plan, trailer)
@@ -1568,7 +1674,7 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
     if not plan['levels']:  # the stored coarsest lowres itself
         x = x[(slice(None), *[slice(s - lo, e - lo) for (s, e), (lo, _) in zip(plan['box'], plan['lowres_axes'])])]
     if q is not None:
-        x = _region_restore(meta, plan, x.contiguous(), local[-3:] if q[2] else None)
+        x = _region_restore(meta, plan, x.contiguous(), local[-nexc:] if q[2] else None)
     elif meta.get('sample_dtype') == 'float32':
         x = x.contiguous().view(torch.float32)
     nbad, ncrc = bad.tolist()  # the synchronisation

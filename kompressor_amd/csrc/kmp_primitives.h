@@ -130,4 +130,12 @@ int launch_maps_from_cell_means(int nsp, int dtype, const void* cm, int64_t B, c
 // Two launches, named "compare"; KMP_ERR_ARG for a dtype it does not take.
 int launch_compare(int dtype, const void* x, const void* r, int64_t n, void* out, int cont, hipStream_t stream);
 
+// kmp_fill.hip: the hold-fill of the marked int16 / int32 array ``x`` into ``out`` (KMP_CODER_FILL; n >= 1,
+// ``ws`` the 8-byte aligned KMP_FILL_BYTES; ``out`` may be ``x``).  Three launches, named "fill"; KMP_ERR_ARG
+// for another dtype.
+int launch_fill(int dtype, const void* x, int64_t n, void* out, void* ws, hipStream_t stream);
+// ... and the patch of the float32 array ``out`` from the R >= 1 records of a run table (KMP_CODER_RUNS).
+// One launch, named "runs".
+int launch_runs(const void* table, int64_t R, void* out, hipStream_t stream);
+
 }  // namespace kmp

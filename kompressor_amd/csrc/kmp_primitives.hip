@@ -793,6 +793,33 @@ int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* p
     KMP_REQUIRE(x && out, "null pointer");
     return launch_compare(x_dtype, x, pred, n, out, field, (hipStream_t)stream);
   }
+  if (coder >= 0 && coder_code(coder) == KMP_CODER_FILL) {
+    // hold-fill of a marked integer array (kmp_fill.hip): pred is the scratch
+    const int64_t w = x_dtype == KMP_I16 ? 2 : 4;
+    KMP_REQUIRE(direction == KMP_ENCODE, "fill: KMP_ENCODE alone");
+    KMP_REQUIRE((coder >> 8) == 0, "fill: the code carries no field");
+    KMP_REQUIRE(x_dtype == KMP_I16 || x_dtype == KMP_I32, "fill takes int16 or int32 arrays");
+    KMP_REQUIRE(pred && ((uintptr_t)pred & 7) == 0, "fill: pred is the 8-byte aligned KMP_FILL_BYTES of scratch");
+    if (n == 0) return KMP_OK;
+    KMP_REQUIRE(x && out, "null pointer");
+    KMP_REQUIRE((((uintptr_t)x | (uintptr_t)out) & (uintptr_t)(w - 1)) == 0, "fill: arrays aligned to their dtype");
+    KMP_REQUIRE(n <= INT64_MAX / 8, "fill: count too large");
+    KMP_REQUIRE(x == out || (uintptr_t)x + (uintptr_t)(n * w) <= (uintptr_t)out ||
+                    (uintptr_t)out + (uintptr_t)(n * w) <= (uintptr_t)x, "fill: x and out overlap in part");
+    return launch_fill(x_dtype, x, n, out, const_cast<void*>(pred), (hipStream_t)stream);
+  }
+  if (coder >= 0 && coder_code(coder) == KMP_CODER_RUNS) {
+    // patch of a float32 array from a run table (kmp_fill.hip): bounds are the caller's duty
+    KMP_REQUIRE(direction == KMP_DECODE, "runs: KMP_DECODE alone");
+    KMP_REQUIRE((coder >> 8) == 0, "runs: the code carries no field");
+    KMP_REQUIRE(x_dtype == KMP_U32, "runs: the table is uint32 (x_dtype KMP_U32)");
+    KMP_REQUIRE(!pred, "runs takes no prediction (pred must be NULL)");
+    if (n == 0) return KMP_OK;
+    KMP_REQUIRE(x && out, "null pointer");
+    KMP_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)out & 3) == 0,
+                "runs: a 16-byte aligned table and a 4-byte aligned array");
+    return launch_runs(x, n, out, (hipStream_t)stream);
+  }
   if (coder >= 0 && is_quant_code(coder_code(coder))) {
     // float32 <-> int16 / int32 on a power-of-two step: no prediction, so none may be passed
     const int code = coder_code(coder);

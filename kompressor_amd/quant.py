@@ -16,7 +16,8 @@ bit.  The arithmetic is ``kmp_code`` with the ``KMP_CODER_QUANT_I16 / _I32`` cod
 when every non-exception fits it, else int32.
 
 The relative mode (``rel_error``) is the second half of the module: ``mantissa_bits``,
-``effective_rel``, ``quantise_rel``, ``restore_rel``.
+``effective_rel``, ``quantise_rel``, ``restore_rel``.  Masked fields are the last part:
+``runs``, ``exceptions_from_runs``, ``fill`` and the device functions the container builds on.
 """
 
 import math
@@ -82,17 +83,28 @@ def d_code(direction, dtype, exp, x):
     return out
 
 
-def d_quantise(x, exp):
-    """``(n, exceptions)`` of the contiguous device float32 tensor ``x``: ``n`` int16 / int32 with 0 at
-    the exceptions, ``exceptions`` None or ``(flat int64 indices ascending, uint32 bits)`` on the device."""
-    n = d_code(_lib.ENCODE, torch.int32, exp, x)
-    mask = n == _SENTINEL[torch.int32]
-    n.masked_fill_(mask, 0)
-    if x.numel() == 0 or int(n.abs().max().item()) <= _I16_MAX:
-        # every non-exception fits int16: the kernel again on that type (the same exception set)
-        n = d_code(_lib.ENCODE, torch.int16, exp, x)
-        mask = n == _SENTINEL[torch.int16]
+def _d_int16_or_int32(encode, x, first, marks):
+    """``(n, exception mask)`` of a quantiser ``encode(dtype)``: ``first`` tried, int16 when every
+    non-exception fits it; 0 at the exceptions, or (``marks``) the type's minimum as ENCODE wrote it."""
+    n = encode(first)
+    mask = n == _SENTINEL[first]
+    if not marks:
         n.masked_fill_(mask, 0)
+    if first == torch.int32 and (x.numel() == 0 or
+                                 int((n.masked_fill(mask, 0) if marks else n).abs().max().item()) <= _I16_MAX):
+        # every non-exception fits int16: the kernel again on that type (the same exception set)
+        n = encode(torch.int16)
+        mask = n == _SENTINEL[torch.int16]
+        if not marks:
+            n.masked_fill_(mask, 0)
+    return n, mask
+
+
+def d_quantise(x, exp, marks=False):
+    """``(n, exceptions)`` of the contiguous device float32 tensor ``x``: ``n`` int16 / int32 with 0 at
+    the exceptions (``marks``: with the type's minimum there, for :func:`d_fill`), ``exceptions`` None or
+    ``(flat int64 indices ascending, uint32 bits)`` on the device."""
+    n, mask = _d_int16_or_int32(lambda dt: d_code(_lib.ENCODE, dt, exp, x), x, torch.int32, marks)
     idx = mask.reshape(-1).nonzero().reshape(-1)
     if idx.numel() == 0:
         return n, None
@@ -216,18 +228,11 @@ def d_code_rel(direction, dtype, bits, x):
     return out
 
 
-def d_quantise_rel(x, bits):
+def d_quantise_rel(x, bits, marks=False):
     """``(n, exceptions)`` of the contiguous device float32 tensor ``x`` with ``bits`` mantissa bits kept:
     as :func:`d_quantise`.  Up to 7 bits every ``n`` fits int16, so that launch is the only one."""
     first = torch.int16 if bits <= _M_ALWAYS_I16 else torch.int32
-    n = d_code_rel(_lib.ENCODE, first, bits, x)
-    mask = n == _SENTINEL[first]
-    n.masked_fill_(mask, 0)
-    if first == torch.int32 and (x.numel() == 0 or int(n.abs().max().item()) <= _I16_MAX):
-        # every non-exception fits int16: the kernel again on that type (the same exception set)
-        n = d_code_rel(_lib.ENCODE, torch.int16, bits, x)
-        mask = n == _SENTINEL[torch.int16]
-        n.masked_fill_(mask, 0)
+    n, mask = _d_int16_or_int32(lambda dt: d_code_rel(_lib.ENCODE, dt, bits, x), x, first, marks)
     idx = mask.reshape(-1).nonzero().reshape(-1)
     if idx.numel() == 0:
         return n, None
@@ -287,3 +292,180 @@ def d_indices(lo, hi):
     """The int64 indices of two uint32 gap-word tensors."""
     g = (lo.view(torch.int32).to(torch.int64) & 0xffffffff) | (hi.view(torch.int32).to(torch.int64) << 32)
     return torch.cumsum(g, 0)
+
+
+# ---------------------------------------------------------------------------------------------
+# masked fields (DESIGN.md §21): exceptions as runs, and the hold-fill of the integers under them
+# ---------------------------------------------------------------------------------------------
+# A run is a maximal stretch of consecutive flat indices whose bits are all equal, none longer than
+# 2**32 - 1.  Stored: the low and high words of the gaps between consecutive run starts (the first gap is
+# the first start), the lengths, and the differences of consecutive runs' bits modulo 2**32 (the first
+# is the first run's bits) -- four uint32 arrays of R entries.  The fill gives every exception's
+# integer the last non-exception's before it (the first one's in a leading stretch, 0 with none): the
+# decoder overwrites those values from the runs, so any value serves and this one costs the pyramid least.
+
+RUN_CAP = (1 << 32) - 1
+
+
+def d_fill(n, out=None):
+    """The hold-fill of the contiguous int16 / int32 device tensor ``n``, whose exceptions hold the type's
+    minimum (as ``kmp_code`` ENCODE of a quantiser writes them): one ``kmp_code`` call (KMP_CODER_FILL).
+    ``out``: the result's tensor (``n`` itself is allowed), a new one by default."""
+    out = dev.empty(n.shape, n.dtype) if out is None else out
+    if n.numel():
+        ws = dev.empty((_lib.FILL_BYTES,), torch.uint8)
+        check(lib.kmp_code(_lib.ENCODE, _lib.CODER_FILL, 0, ws.data_ptr(), dev.dtype_code(n), n.data_ptr(), n.numel(),
+                           out.data_ptr(), dev.stream()), 'code')
+    return out
+
+
+def d_mark(n, exceptions):
+    """``n`` itself with the type's minimum written at the ``exceptions`` (in place): what ENCODE wrote."""
+    if exceptions is not None:
+        n.reshape(-1)[exceptions[0]] = _SENTINEL[n.dtype]
+    return n
+
+
+def _cut(starts, lengths, bits, piece):
+    """Runs no longer than ``piece``: every longer one cut into pieces from its start (int64 tensors)."""
+    if starts.numel() == 0 or int(lengths.max().item()) <= piece:
+        return starts, lengths, bits
+    k = (lengths + (piece - 1)) // piece
+    rep = torch.repeat_interleave(torch.arange(k.numel(), device=k.device), k)
+    first = torch.cumsum(k, 0) - k
+    at = (torch.arange(rep.numel(), device=k.device) - first[rep]) * piece
+    return starts[rep] + at, torch.clamp(lengths[rep] - at, max=piece), bits[rep]
+
+
+def d_run_list(idx, bits, cap=RUN_CAP):
+    """``(starts, lengths, bits)`` (int64 device tensors, the bits in [0, 2**32)) of the runs of the sorted
+    int64 indices ``idx`` and their uint32 ``bits``."""
+    b = bits.view(torch.int32)
+    new = torch.ones(idx.shape, dtype=torch.bool, device=idx.device)
+    new[1:] = ((idx[1:] - idx[:-1]) != 1) | (b[1:] != b[:-1])
+    first = new.nonzero().reshape(-1)
+    lengths = torch.diff(first, append=torch.tensor([idx.numel()], device=idx.device))
+    return _cut(idx[first], lengths, b[first].to(torch.int64) & 0xffffffff, cap)
+
+
+def d_runs(idx, bits):
+    """``(start gaps low, high, lengths, bit deltas)`` (uint32 device tensors) of the exceptions ``(idx, bits)``."""
+    starts, lengths, rb = d_run_list(idx, bits)
+    delta = rb.clone()
+    delta[1:] -= rb[:-1]
+    return (*d_gaps(starts), _low32(lengths), _low32(delta))
+
+
+def d_run_starts(lo, hi, lengths, delta):
+    """``(starts, lengths, bits)`` (int64 device tensors, the bits in [0, 2**32)) of the four stored arrays."""
+    def wide(v):
+        return v.view(torch.int32).to(torch.int64) & 0xffffffff
+    return d_indices(lo, hi), wide(lengths), torch.cumsum(wide(delta), 0) & 0xffffffff
+
+
+def d_check_runs(starts, lengths, numel):
+    """ValueError unless every run has ``length >= 1`` and lies inside ``[0, numel)`` and the runs ascend
+    without overlap: one read-back.  No sum of a start and a length is formed before the start is known to
+    be inside the array, so a start near 2**63 (a damaged file's gap words reach any int64) cannot wrap
+    past the comparison: ``numel - start`` is exact for ``0 <= start``, and the difference of two
+    starts is exact once both lie in ``[0, numel]``."""
+    if starts.numel():
+        ok = (starts >= 0) & (lengths >= 1) & (lengths <= numel - starts)
+        # only read where both neighbours are inside: elsewhere ``ok`` already fails
+        ordered = (starts[1:] - starts[:-1]) >= lengths[:-1]
+        if not bool((ok.all() & ordered.all()).item()):
+            raise ValueError('an exception run is empty, lies outside the array or overlaps another')
+
+
+def d_table(starts, lengths, bits, piece=_lib.RUNS_PIECE):
+    """The ``(R', 4)`` uint32 device table of KMP_CODER_RUNS -- start low, start high, length, bits per
+    record -- of checked runs, every run longer than ``piece`` cut into records of at most ``piece``."""
+    starts, lengths, bits = _cut(starts, lengths, bits, piece)
+    cols = [_low32(starts), _low32(starts >> 32), _low32(lengths), _low32(bits)]
+    return torch.stack([c.view(torch.int32) for c in cols], 1).contiguous().view(torch.uint32)
+
+
+def d_run_table(lo, hi, lengths, delta, numel, piece=_lib.RUNS_PIECE):
+    """:func:`d_table` of the four stored arrays, the runs' extents checked against ``numel`` first."""
+    runs_ = d_run_starts(lo, hi, lengths, delta)
+    d_check_runs(runs_[0], runs_[1], numel)
+    return d_table(*runs_, piece)
+
+
+def d_patch_runs(out, table):
+    """The contiguous float32 device tensor ``out`` patched in place from ``table`` (:func:`d_run_table`, whose
+    check is what keeps the writes inside ``out``): one ``kmp_code`` call (KMP_CODER_RUNS)."""
+    if table.shape[0]:
+        check(lib.kmp_code(_lib.DECODE, _lib.CODER_RUNS, 0, None, _lib.U32, table.data_ptr(), table.shape[0],
+                           out.data_ptr(), dev.stream()), 'code')
+    return out
+
+
+def d_expand(starts, lengths, bits):
+    """``(int64 indices ascending, uint32 bits)`` of runs (int64 tensors, as :func:`d_run_starts`)."""
+    rep = torch.repeat_interleave(torch.arange(starts.numel(), device=starts.device), lengths)
+    first = torch.cumsum(lengths, 0) - lengths
+    idx = starts[rep] + torch.arange(rep.numel(), device=starts.device) - first[rep]
+    return idx, _low32(bits[rep])
+
+
+def _require_runs(arrays, who):
+    """TypeError / ValueError unless ``arrays`` are four 1-d uint32 arrays of one length: no device work."""
+    if len(arrays) != 4:
+        raise ValueError(f'{who}: runs are four arrays (start gaps low, high, lengths, bit deltas)')
+    for a in arrays:
+        if _input_dtype(a) not in (torch.uint32, np.dtype(np.uint32)):
+            raise TypeError(f'{who}: the run arrays are uint32')
+    if any(len(a.shape) != 1 or a.shape != arrays[0].shape for a in arrays):
+        raise ValueError(f'{who}: the run arrays are 1-d and of one length')
+
+
+def _require_exceptions(exceptions, who):
+    idx, bits = exceptions
+    if _input_dtype(idx) not in (torch.int64, np.dtype(np.int64)) or \
+            _input_dtype(bits) not in (torch.uint32, np.dtype(np.uint32)):
+        raise TypeError(f'{who}: exceptions are (int64 indices, uint32 bits)')
+    if len(idx.shape) != 1 or idx.shape != bits.shape:
+        raise ValueError(f'{who}: indices and bits are two 1-d arrays of one length')
+
+
+def _index_tensor(idx):
+    return idx.to('cuda') if isinstance(idx, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(idx)).to('cuda')
+
+
+def runs(exceptions):
+    """The stored form ``(start gaps low, high, lengths, bit deltas)`` -- four uint32 arrays -- of the
+    ``exceptions`` ``(int64 indices ascending, uint32 bits)`` that ``quantise`` / ``quantise_rel`` return.
+    numpy in gives numpy out, CUDA tensors in give CUDA tensors out."""
+    _require_exceptions(exceptions, 'quant.runs')
+    kind = 'torch' if isinstance(exceptions[0], torch.Tensor) else 'numpy'
+    dev.require_gpu()
+    out = d_runs(_index_tensor(exceptions[0]), dev.to_device(exceptions[1])[0])
+    return tuple(dev.from_device(a, kind) for a in out)
+
+
+def exceptions_from_runs(lo, hi, lengths, delta):
+    """``(int64 indices ascending, uint32 bits)``: the runs of :func:`runs` expanded.  A run of length 0
+    is ValueError."""
+    arrays = (lo, hi, lengths, delta)
+    _require_runs(arrays, 'quant.exceptions_from_runs')
+    kind = 'torch' if isinstance(lo, torch.Tensor) else 'numpy'
+    starts, lens, bits = d_run_starts(*[dev.to_device(a)[0] for a in arrays])
+    if lens.numel() and int(lens.min().item()) < 1:
+        raise ValueError('quant.exceptions_from_runs: a run of length 0')
+    idx, b = d_expand(starts, lens, bits)
+    return dev.from_device(idx, kind), dev.from_device(b, kind)
+
+
+def fill(n, exceptions=None):
+    """``n`` (int16 / int32, as ``quantise`` returns it) with the value at every exception replaced by the
+    last non-exception's before it in flat C order -- the first one's before the first, 0 with none.
+    ``restore`` of the result with the same exceptions is ``restore`` of ``n``."""
+    _require_quantised(n, exceptions, 'quant.fill')
+    if exceptions is not None:
+        _require_exceptions(exceptions, 'quant.fill')
+    nt, kind = dev.to_device(n)
+    exc = _device_exceptions(nt, exceptions, 'quant.fill')
+    if exc is None:
+        return dev.from_device(nt, kind)
+    return dev.from_device(d_fill(d_mark(nt.clone(), exc)), kind)

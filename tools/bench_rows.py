@@ -668,6 +668,65 @@ def main():
             print(json.dumps(line), flush=True)
         del work, routes
 
+    # Masked fields (only with --rows fill): the hold-fill (kmp_code with KMP_CODER_FILL: the
+    # array read twice and written once) on 512 x 64^3 int16 and int32 with a 10 % slab and with 1 % scattered
+    # elements marked, and the patch from the run table of the same masks (KMP_CODER_RUNS) on the float32
+    # array, each against a device copy of the array's bytes (read once, written once), alternated in one
+    # process, 9 samples of --reps calls.
+    if 'fill' in want:
+        from kompressor_amd import _device as dev, quant
+        n = 512 * 64 ** 3
+        gen = torch.Generator(device='cuda').manual_seed(0)
+        masks = {'slab10': torch.zeros(n, dtype=torch.bool, device='cuda'),
+                 'scattered1': torch.rand(n, device='cuda', generator=gen) < 0.01}
+        masks['slab10'][n // 3:n // 3 + n // 10] = True
+        routes, moved, what = {}, {}, {}
+        for tdt in (torch.int16, torch.int32):
+            tname = 'int16' if tdt == torch.int16 else 'int32'
+            base = torch.randint(-3000, 3000, (n,), device='cuda', generator=gen).to(tdt)
+            src = torch.empty(n * base.element_size(), dtype=torch.uint8, device='cuda')
+            dst = torch.empty_like(src)
+            for mname, mask in masks.items():
+                marked = base.masked_fill(mask, torch.iinfo(tdt).min)
+                out = torch.empty_like(marked)
+                tag = f'fill:{tname}:{mname}'
+                routes[tag] = {'fill': lambda marked=marked, out=out: quant.d_fill(marked, out),
+                               'copy': lambda src=src, dst=dst: dst.copy_(src)}
+                moved[tag], what[tag] = 3 * n * base.element_size(), f'512 x 64^3 {tname}, {int(mask.sum().item())} marked'
+                quant.d_fill(marked, out)
+                keep = ~mask
+                assert torch.equal(out[keep], base[keep]) and int((out == torch.iinfo(tdt).min).sum().item()) == 0
+                del keep
+        f32 = torch.zeros(n, dtype=torch.float32, device='cuda')
+        src = torch.empty(n * 4, dtype=torch.uint8, device='cuda')
+        dst = torch.empty_like(src)
+        for mname, mask in masks.items():
+            idx = mask.nonzero().reshape(-1)
+            bits = torch.full((idx.numel(),), 0x7fc00000, dtype=torch.int32, device='cuda').view(torch.uint32)
+            table = quant.d_run_table(*quant.d_runs(idx, bits), n)
+            tag = f'runs:float32:{mname}'
+            routes[tag] = {'runs': lambda table=table: quant.d_patch_runs(f32, table),
+                           'copy': lambda src=src, dst=dst: dst.copy_(src)}
+            moved[tag], what[tag] = 4 * idx.numel() + 16 * table.shape[0], \
+                f'512 x 64^3 float32, {idx.numel()} elements in {table.shape[0]} records'
+            f32.zero_()
+            quant.d_patch_runs(f32, table)
+            assert torch.equal(f32.view(torch.int32) == 0x7fc00000, mask)
+        samples = {(t, d): [] for t in routes for d in routes[t]}
+        for _ in range(9):
+            for t in routes:
+                for d in routes[t]:
+                    samples[(t, d)].append(gpu_time(routes[t][d], args.reps))
+        med = {k: float(np.median(v)) for k, v in samples.items()}
+        for (t, d), v in samples.items():
+            line = {'row': f'{t}:{d}', 'what': what[t], 'us': round(med[(t, d)] * 1e6, 1),
+                    'us_min': round(min(v) * 1e6, 1), 'us_max': round(max(v) * 1e6, 1), 'samples': len(v),
+                    'ratio_to_copy': round(med[(t, d)] / med[(t, 'copy')], 4)}
+            if d != 'copy':
+                line['TBps'] = round(moved[t] / med[(t, d)] / 1e12, 3)
+            print(json.dumps(line), flush=True)
+        del routes, masks, f32
+
     # The comparing call (only with --rows compare): kmp_code with KMP_CODER_COMPARE on a 512^3
     # float32 field and on 512 x 64^3 uint16 tiles against the torch composition the bound checks run for
     # the same arrays (container._quant_max_error / near.d_max_abs_error without their restoring launch),

@@ -1,7 +1,8 @@
 """compress / decompress of a 512^3 float32 smooth-plus-noise field at abs_error None, 1e-1, 1e-2, 1e-3:
 file size, bits per sample and the last_timing splits; three timed rounds, the bounds alternated within
 each.  ``--nan`` turns about 10 % of the volume (a slab of planes) into NaN: the cost of the exception
-path.  ``--lossless-only`` runs the ``None`` row alone and passes no keyword, so the same script
+path; ``--runs`` next to it stores the exceptions as runs over hold-filled integers (DESIGN.md §21:
+``exceptions='runs'`` at every bound).  ``--lossless-only`` runs the ``None`` row alone and passes no keyword, so the same script
 measures a build from before error-bounded coding.  ``--rel`` measures the relative mode instead
 (DESIGN.md §18): the field becomes ``10 ** (2 f)`` -- four decades -- times ``1 + noise / 15``, and the
 bounds are ``rel_error`` None, 1e-1, 1e-2, 1e-3.  ``--target`` measures rate control instead (DESIGN.md
@@ -25,6 +26,7 @@ for _ in range(4):
 f /= np.abs(f).max()
 x = (f + rng.standard_normal((n, n, n), dtype=np.float32) / 15).astype(np.float32)  # noise 1/15 of the amplitude
 REL = '--rel' in sys.argv
+RUNS = {'exceptions': 'runs'} if '--runs' in sys.argv else {}
 KEY, MAX = ('rel_error', 'max_rel_error') if REL else ('abs_error', 'max_abs_error')
 if REL:  # multiplicative noise on a field that spans four decades
     x = (np.power(np.float32(10), 2 * f) * (1 + rng.standard_normal((n, n, n), dtype=np.float32) / 15)).astype(np.float32)
@@ -105,7 +107,7 @@ if '--psnr' in sys.argv:
 for rnd in range(4):
     for a in bounds:
         path = os.path.join(d, 'v.kmp')
-        res = container.compress(path, xt, pred, levels=3, **({} if a is None else {KEY: a}))
+        res = container.compress(path, xt, pred, levels=3, **({} if a is None else {KEY: a, **RUNS}))
         tc = dict(container.last_timing)
         torch.cuda.synchronize()
         y = container.decompress(path, as_numpy=False)
@@ -126,9 +128,9 @@ for rnd in range(4):
 for a, runs in out.items():
     med = lambda xs: float(np.median(xs))
     res = runs[0][0]
-    line = {KEY: a, 'nan_slab': '--nan' in sys.argv, 'bytes': res['bytes'],
+    line = {KEY: a, 'nan_slab': '--nan' in sys.argv, 'runs': bool(RUNS), 'bytes': res['bytes'],
             'bits_per_sample': round(res['bits_per_sample'], 4),
-            **{k: res[k] for k in (KEY, MAX, 'exceptions', 'quant_dtype') if k in res and a is not None},
+            **{k: res[k] for k in (KEY, MAX, 'exceptions', 'exception_runs', 'quant_dtype') if k in res and a is not None},
             KEY + '_asked': a,
             'compress_ms': {k: [round(1e3 * f([r[1][k] for r in runs]), 2) for f in (med, min, max)] for k in runs[0][1]},
             'decompress_ms': {k: [round(1e3 * f([r[2][k] for r in runs]), 2) for f in (med, min, max)]
