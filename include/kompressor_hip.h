@@ -139,7 +139,23 @@ typedef enum {
      KMP_ENCODE, another x_dtype, a non-zero field above the low byte, a non-NULL ``pred``, a misaligned
      table or array, or this code on any other entry point.  R == 0 is KMP_OK.  One launch;
      kmp_last_launch() names it "runs". */
-  KMP_CODER_RUNS = 12
+  KMP_CODER_RUNS = 12,
+  /* Delta of two integer arrays modulo 2^W (kmp_code alone): the step of time-series coding
+     along the batch axis.  ``x`` and ``pred`` (non-NULL whatever the count) are arrays of ``x_dtype`` ==
+     ``pred_dtype``, one of KMP_U8, KMP_I8, KMP_U16, KMP_I16, KMP_I32, W its width; ``out`` has the same dtype
+     and count.  ENCODE writes out[i] = (x[i] - pred[i]) mod 2^W, DECODE out[i] = (x[i] + pred[i]) mod 2^W:
+     signed and unsigned samples of one width give the same bits.  ``out`` may be ``x`` itself (a lane loads
+     what it stores before it stores it); any other overlap of ``out`` with ``x``, and any overlap of ``out``
+     with ``pred``, is refused.  All three pointers 16-byte aligned and n a multiple of 16 / sizeof(sample):
+     16-byte non-temporal accesses; anything else (the dtype's alignment at least): element accesses.  One
+     launch on ``stream``, no atomics, no LDS, no workspace; the same buffers give the same bytes on every call.
+     A sequence of T frames of F samples: the encode of every frame against the one before it is ONE call
+     (x = n + F, pred = n, count (T - 1) F, out of place); the decode is one call per frame, in order,
+     ``pred`` the frame just restored.  KMP_ERR_ARG, with nothing launched: a NULL ``pred`` (whatever the
+     count), a non-zero field above the low byte, differing or other dtypes, a direction other than
+     KMP_ENCODE / KMP_DECODE, arrays not aligned to their dtype, a refused overlap, or this code on any
+     other entry point.  n == 0 is KMP_OK and touches nothing.  kmp_last_launch() names it "delta". */
+  KMP_CODER_DELTA = 13
 } kmp_coder;
 #define KMP_CODER_NEAR(code, max_error) ((code) | ((max_error) << 8))
 #define KMP_CODER_QUANT(code, exp) ((code) | (((exp) + 127) << 8))
@@ -364,7 +380,9 @@ int kmp_tiles(int32_t nsp, int32_t dtype, int32_t direction, const void* src, co
    ``out`` the KMP_COMPARE_BYTES of the error statistics; ENCODE alone.
    KMP_CODER_FILL (see kmp_coder): ``x`` the marked int16 / int32 array, ``out`` the filled one, ``pred`` the
    KMP_FILL_BYTES of scratch; ENCODE alone.  KMP_CODER_RUNS (see kmp_coder): ``x`` the run table (n records),
-   ``out`` the float32 array patched in place, ``pred`` NULL; DECODE alone. */
+   ``out`` the float32 array patched in place, ``pred`` NULL; DECODE alone.
+   KMP_CODER_DELTA (see kmp_coder): ``x`` and ``pred`` two integer arrays of one dtype, ``out`` their
+   difference (ENCODE) or sum (DECODE) modulo 2^W in that dtype. */
 int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* pred, int32_t x_dtype,
              const void* x, int64_t n, void* out, kmp_stream_t stream);
 

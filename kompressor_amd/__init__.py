@@ -11,7 +11,7 @@ in ``libkompressor_hip.so`` (hand-written gfx950 kernels behind the C-ABI in
 """
 
 from . import _lib  # noqa: F401  (fails loudly if libkompressor_hip.so is missing)
-from . import image, volume, predictors, utils, near, quant, rate, metrics, tiles, shard, slabs, stream, packing, container, graphs  # noqa: F401
+from . import image, volume, predictors, utils, near, quant, delta, rate, metrics, tiles, shard, slabs, stream, packing, container, graphs  # noqa: F401
 from .predictors import MeanPredictor, LinearPredictor, linear_moments, solve_moments  # noqa: F401
 from ._device import release_pinned  # noqa: F401
 

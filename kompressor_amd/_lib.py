@@ -86,6 +86,11 @@ def fill_span(n):
     return -(-tiles // FILL_GROUPS) * FILL_TILE
 
 
+# time series (kmp_code alone): out = x - pred (ENCODE) or x + pred (DECODE) modulo 2^W of two
+# arrays of one integer dtype (U8, I8, U16, I16, I32); ``out`` may be ``x``
+CODER_DELTA = 13
+
+
 def coder_code(coder):
     return int(coder) & 0xff
 

@@ -27,8 +27,9 @@ and a failing ``decompress`` name the damaged ones.  ``bundle_bytes`` and ``crc3
 alone either way, and a reader that does not know the key reads the file as before.
 Version 4 is a near-lossless file (``'max_error'``), version 5 an error-bounded float32 file
 (``'quant'``, and its exception arrays behind the maps), version 6 a relative-error float32 file
-(``'prec'``), version 7 either of the two with its exceptions stored as runs (``'exception_runs'``); see
-``VERSION_NEAR`` / ``VERSION_QUANT`` / ``VERSION_PREC`` / ``VERSION_RUNS`` below.
+(``'prec'``), version 7 either of the two with its exceptions stored as runs (``'exception_runs'``), version 8
+a time series, delta-coded along the batch axis (``'temporal'``); see ``VERSION_NEAR`` / ``VERSION_QUANT`` /
+``VERSION_PREC`` / ``VERSION_RUNS`` / ``VERSION_TEMPORAL`` below.
 
 The host side of the file path (round 4): the bundle's CRC-32 (zlib's, the value the file stores)
 is computed on the device (``kmp_crc32``) -- over the bundle the encode just wrote, its length read
@@ -48,7 +49,7 @@ import numpy as np
 import torch
 
 from . import _device as dev
-from . import _nd, metrics, near, packing, quant, rate
+from . import _nd, delta, metrics, near, packing, quant, rate
 from ._lib import DECODE as _lib_decode, check as _check, coder_max_error as _lib_max_error, lib
 from .predictors import ARITH_REV, LinearPredictor, MeanPredictor
 
@@ -79,6 +80,16 @@ VERSION_PREC = 6
 # consecutive run starts, the lengths, the differences of consecutive runs' bits modulo 2^32.  Older builds
 # refuse version 7; with E == 0 the file is the version-5 / 6 one, byte for byte.
 VERSION_RUNS = 7
+# 8: a time series (``temporal='delta'``): the batch axis is time and the coded integers are the
+# deltas ``kom.delta`` takes along it.  The metadata is that of the version the file would otherwise be (3, 5,
+# 6 or 7: none, 'quant', 'prec', or one of them with 'exception_runs') plus 'temporal' = {'mode': 'delta',
+# 'key_interval': K or 0 (only frame 0 is a key frame), 'dtype': the deltas' dtype -- the signed one of the
+# samples' width, for a float32 file the quantiser's}.  The bundle's arrays are those of that version with the
+# deltas in place of the integers.  Never a 'max_error'.  Older builds refuse version 8; without the keyword,
+# and for a single frame, the file is the other version's byte for byte.
+VERSION_TEMPORAL = 8
+_TEMPORAL = (None, 'delta')
+_TEMPORAL_DTYPES = {'int8': torch.int8, 'int16': torch.int16, 'int32': torch.int32}
 _EXCEPTIONS = ('list', 'runs')
 _QUANT_DTYPES ={'int16': torch.int16, 'int32': torch.int32}
 _QUANT_SLAB = 1 << 24  # elements per slab of the bound's check
@@ -184,6 +195,48 @@ def _check_runs(meta, version, path):
         raise ValueError(f'{path}: a version-{VERSION_RUNS} (exception runs) file with a bad exception_runs entry '
                          f'{R!r} ({E} exceptions)')
     return base
+
+
+def _check_temporal(meta, version, path):
+    """The version whose rules the rest of the metadata follows.  A version-8 file carries a well-formed
+    'temporal' and no 'max_error'; the rest is a version-3, -5, -6 or -7 file's, told apart by its 'quant',
+    'prec' and 'exception_runs' entries.  No other version has a 'temporal'."""
+    t = meta.get('temporal') if isinstance(meta, dict) else None
+    if version != VERSION_TEMPORAL:
+        if isinstance(meta, dict) and 'temporal' in meta:
+            raise ValueError(f'{path}: a version-{version} file with a temporal entry (time series are version '
+                             f'{VERSION_TEMPORAL})')
+        return version
+    if 'max_error' in meta:
+        raise ValueError(f'{path}: a version-{VERSION_TEMPORAL} (time series) file with a max_error entry')
+    K = t.get('key_interval') if isinstance(t, dict) else None
+    if not (isinstance(t, dict) and t.get('mode') == 'delta' and isinstance(K, int) and not isinstance(K, bool) and
+            K >= 0 and isinstance(t.get('dtype'), str) and t['dtype'] in _TEMPORAL_DTYPES):
+        raise ValueError(f'{path}: a version-{VERSION_TEMPORAL} (time series) file with a bad temporal entry {t!r}')
+    if 'exception_runs' in meta:
+        base = VERSION_RUNS
+    else:
+        base = VERSION_QUANT if 'quant' in meta else VERSION_PREC if 'prec' in meta else VERSION
+    q = meta.get('quant') or meta.get('prec')
+    name = q.get('dtype') if isinstance(q, dict) else meta.get('sample_dtype')
+    want = _NP_NAME.get(delta.SIGNED.get(delta.NAMES.get(name)))
+    if t['dtype'] != want:
+        raise ValueError(f'{path}: a version-{VERSION_TEMPORAL} (time series) file whose deltas are {t["dtype"]!r}: '
+                         f'those of {name!r} values are {want!r}')
+    return base
+
+
+def _temporal(meta):
+    """``(K or None, the deltas' torch dtype)`` of a time series whose header ``_read_head`` accepted, else None."""
+    t = meta.get('temporal')
+    if t is None:
+        return None
+    return (int(t['key_interval']) or None), _TEMPORAL_DTYPES[t['dtype']]
+
+
+def _versioned(meta, version):
+    """The version a file of ``meta`` is written as: ``version``, or 8 for a time series."""
+    return VERSION_TEMPORAL if 'temporal' in meta else version
 
 
 def _runs(meta):
@@ -401,8 +454,8 @@ def _read_head(f, path):
     if len(head) < _HEAD.size:
         raise ValueError(f'{path}: not a kompressor_amd file (too short)')
     magic, version, _, mlen = _HEAD.unpack(head)
-    if magic != MAGIC or version not in (1, 2, VERSION, VERSION_NEAR, VERSION_QUANT, VERSION_PREC, VERSION_RUNS) or \
-            mlen > (1 << 26):
+    if magic != MAGIC or version not in (1, 2, VERSION, VERSION_NEAR, VERSION_QUANT, VERSION_PREC, VERSION_RUNS,
+                                         VERSION_TEMPORAL) or mlen > (1 << 26):
         raise ValueError(f'{path}: not a kompressor_amd file (magic {magic!r}, version {version})')
     try:
         meta = json.loads(f.read(mlen).decode())
@@ -410,7 +463,8 @@ def _read_head(f, path):
     except (ValueError, KeyError, TypeError) as e:
         raise ValueError(f'{path}: corrupt metadata ({e})') from None
     _check_sample_dtype(meta, path)
-    base = _check_runs(meta, version, path)  # a version-7 file follows version 5's or 6's rules
+    base = _check_temporal(meta, version, path)  # a version-8 file follows version 3's, 5's, 6's or 7's rules
+    base = _check_runs(meta, base, path)  # a version-7 file follows version 5's or 6's rules
     _check_max_error(meta, base, path)
     _check_quant(meta, base, path)
     _check_prec(meta, base, path)
@@ -577,8 +631,37 @@ def _check_exceptions(exceptions, abs_error, rel_error, mode=None):
     return exceptions == 'runs'
 
 
+def _check_temporal_args(highres, temporal, key_interval, max_error, abs_error, rel_error, mode=None):
+    """The ``temporal`` / ``key_interval`` keywords of a ``compress`` / ``compressed_size`` call, checked on the
+    host alone: None, or ``(K or None,)`` for a time series.  ValueError for a ``temporal`` other than None /
+    'delta', a ``key_interval`` without it or one that is a bool, no int or < 1, 'delta' with a near-lossless
+    bound (a per-frame error would add up along the chain) and 'delta' for lossless float32 / uint32 samples."""
+    if isinstance(temporal, (bool, bytes)) or temporal not in _TEMPORAL:
+        raise ValueError(f"temporal must be None or 'delta', got {temporal!r}")
+    if temporal is None:
+        if key_interval is not None:
+            raise ValueError("key_interval needs temporal='delta'")
+        return None
+    K = delta.check_key_interval(key_interval)
+    if max_error or mode == 'near':
+        raise ValueError("temporal='delta' does not go with max_error or a near-lossless target: the per-frame "
+                         'errors would add up along the chain')
+    if abs_error is None and rel_error is None and mode is None:
+        try:
+            delta.sample_dtype(near._input_dtype(highres), "compress(temporal='delta')")
+        except TypeError as e:
+            raise ValueError(f'{e} (float32 samples: with abs_error, rel_error or a target)') from None
+    return (K,)
+
+
+def _single_frame(tk, h):
+    """``tk`` for the device tensor ``h``: a series of one frame (or none) is the ordinary file."""
+    return tk if tk is not None and h.shape[0] > 1 else None
+
+
 def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None,
-             rel_error=None, target_bits=None, target_ratio=None, target_mode=None, target_psnr=None, exceptions='list'):
+             rel_error=None, target_bits=None, target_ratio=None, target_mode=None, target_psnr=None, exceptions='list',
+             temporal=None, key_interval=None):
     """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
     :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int8 / int16
     modular on the sign-mapped samples, int32 raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
@@ -628,51 +711,78 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
     (``quant.runs``) instead of one index and 32 bits each, and the integers under them are hold-filled
     (``quant.fill``) so that a hole costs the pyramid next to nothing.  What :func:`decompress` returns is bit
     for bit what the ``'list'`` file returns.  With exceptions the file is version 7; without any it is the
-    ``'list'`` file byte for byte.  The result also holds ``'exception_runs'``."""
+    ``'list'`` file byte for byte.  The result also holds ``'exception_runs'``.
+    ``temporal='delta'`` (not with ``max_error`` or a near-lossless target, not for lossless
+    float32 / uint32 samples): a time series -- the batch axis is time and every frame but the key frames is
+    coded as its difference from the frame before it, modulo 2^W, on the integers (``kom.delta``: the
+    samples of a lossless file, for a float32 file the quantiser's integers after marks and fill), then the
+    unchanged pyramid.  ``key_interval = K``: frame ``t`` is a key frame iff ``t % K == 0``; None: frame 0 alone
+    (``key_interval`` without ``temporal`` is ValueError).  What :func:`decompress` returns is bit for bit what
+    the same call without ``temporal`` returns, and every bound is checked on exactly that; ``read_region``
+    of frames ``a .. b`` decodes from the key frame at or before ``a``.  The file is version 8 and the result
+    also holds ``'temporal'`` and ``'key_interval'``; a single frame writes the ordinary file, byte for byte."""
     mode = rate.check_target(near._input_dtype(highres), target_bits, target_ratio, target_mode, method, max_error,
                              abs_error, rel_error, target_psnr)  # before the device is touched
     exp, bits = _check_bounds(highres, max_error, abs_error, rel_error)  # before the device is touched
     runs = _check_exceptions(exceptions, abs_error, rel_error, mode)  # before the device is touched
+    tk = _check_temporal_args(highres, temporal, key_interval, max_error, abs_error, rel_error, mode)  # likewise
     t0 = time.perf_counter()
     packing._check_method(method)
     _check_tile_crc_method(tile_crc, method)
     h, _ = dev.to_device(highres)
+    tk = _single_frame(tk, h)
     if target_psnr is not None:
-        return _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, float(target_psnr), t0, runs)
+        return _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, float(target_psnr), t0, runs, tk)
     if mode is not None:
-        return _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0, runs)
+        return _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0, runs, tk)
     if max_error:
         return _compress_near(path, h, predictor, levels, method, tile_crc, int(max_error), t0)
     if exp is not None:
-        return _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0, runs)
+        return _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0, runs, tk)
     if bits is not None:
-        return _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0, runs)
-    return _compress_lossless(path, h, predictor, levels, method, tile_crc, t0)
+        return _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0, runs, tk)
+    return _compress_lossless(path, h, predictor, levels, method, tile_crc, t0, tk)
 
 
-def _compress_lossless(path, h, predictor, levels, method, tile_crc, t0):
-    """:func:`compress` without a bound: the lossless pyramid, the version-3 file."""
-    p = _parts_lossless(h, predictor, levels, method)
+def _temporal_meta(tk, d):
+    """The metadata's 'temporal' entry of the deltas ``d`` taken under ``tk``."""
+    return {'mode': 'delta', 'key_interval': tk[0] or 0, 'dtype': _NP_NAME[d.dtype]}
+
+
+def _temporal_result(tk):
+    """What a :func:`compress` result says of a time series."""
+    return {} if tk is None else {'temporal': 'delta', 'key_interval': tk[0]}
+
+
+def _compress_lossless(path, h, predictor, levels, method, tile_crc, t0, tk=None):
+    """:func:`compress` without a bound: the lossless pyramid, the version-3 file (``tk``: of the deltas along
+    the batch axis, the version-8 file)."""
+    p = _parts_lossless(h, predictor, levels, method, tk)
     blob, total, crc, table = _bundle(p['x'], p['arrays'], (), method, tile_crc)
-    nbytes = _write(path, p['meta'], blob, total, crc, t0, table)
+    nbytes = _write(path, p['meta'], blob, total, crc, t0, table, _versioned(p['meta'], VERSION))
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
-            'levels': p['levels'], 'max_error': 0, 'max_abs_error': 0, 'mse': 0.0, 'psnr': float('inf')}
+            'levels': p['levels'], 'max_error': 0, 'max_abs_error': 0, 'mse': 0.0, 'psnr': float('inf'),
+            **_temporal_result(tk)}
 
 
 # The arrays and the metadata of a file, before anything is entropy-coded: what :func:`compress` bundles
 # and writes and what :func:`compressed_size` only measures.  Each returns {'x': the coarsest lowres,
 # 'arrays': the bundle's arrays after it, 'meta', 'levels'} and its mode's own entries.
 
-def _parts_lossless(h, predictor, levels, method):
+def _parts_lossless(h, predictor, levels, method, tk=None):
     ndim, padding = predictor.ndim, predictor.padding
     sample = _NP_NAME[h.dtype]
     if h.dtype == torch.float32:
         h = h.view(torch.uint32)
+    if tk is not None:  # a time series: the pyramid of the deltas, in the signed dtype of the samples' width
+        h = delta.d_encode(h, tk[0])
     x, arrays, meta_levels, levels = _lossless_levels(h, predictor, levels)
     meta = {'format': 'kompressor_amd', 'ndim': ndim, 'padding': padding, 'method': method,
             'sample_dtype': sample, 'levels': meta_levels, 'lowres_shape': list(x.shape),
             'predictor': _predictor_meta(predictor, padding, ndim, x.dtype)}
+    if tk is not None:
+        meta['temporal'] = _temporal_meta(tk, h)
     # one bundle: the coarsest lowres, then every level's maps finest first (no bundle dims: the
     # per-level dims live in the metadata)
     return {'x': x, 'arrays': arrays, 'meta': meta, 'levels': levels}
@@ -753,16 +863,17 @@ def _quant_max_error(h, n, exp, exceptions):
     return float(worst.item())
 
 
-def _parts_quantised(h, predictor, levels, method, key, param, value, quantise, runs=False):
+def _parts_quantised(h, predictor, levels, method, key, param, value, quantise, runs=False, tk=None):
     """The quantiser (``quantise(h, value)``), the lossless pyramid of its integers ``'n'``, the
     exceptions ``'exc'`` (``'E'`` of them) behind the maps, the metadata's ``key`` entry.  ``runs``: the
-    integers under the exceptions are hold-filled and the exceptions ride as ``'R'`` runs."""
+    integers under the exceptions are hold-filled and the exceptions ride as ``'R'`` runs.  ``tk``: a time
+    series -- the pyramid is that of the deltas of ``'n'`` (as the file restores it: after marks and fill)."""
     ndim, padding = predictor.ndim, predictor.padding
     n, exc = quantise(h, value, marks=runs)  # runs: the marks ENCODE wrote stay in n
     E = 0 if exc is None else int(exc[0].numel())
     if E and runs:  # n is this call's own tensor: filled in place (kmp_code allows out == x for the fill)
         n = quant.d_fill(n, out=n)
-    x, arrays, meta_levels, levels = _lossless_levels(n, predictor, levels)
+    x, arrays, meta_levels, levels = _lossless_levels(n if tk is None else delta.d_encode(n, tk[0]), predictor, levels)
     R = 0
     if E and runs:  # the runs ride behind the maps: start gap words (low, high), lengths, bit deltas
         stored = quant.d_runs(*exc)
@@ -775,21 +886,23 @@ def _parts_quantised(h, predictor, levels, method, key, param, value, quantise, 
             key: {param: value, 'dtype': _NP_NAME[n.dtype], 'exceptions': E}}
     if R:
         meta['exception_runs'] = R
+    if tk is not None:
+        meta['temporal'] = _temporal_meta(tk, n)
     return {'x': x, 'arrays': arrays, 'meta': meta, 'levels': levels, 'n': n, 'exc': exc, 'E': E, 'R': R}
 
 
-def _parts_quant(h, predictor, levels, method, exp, runs=False):
-    return _parts_quantised(h, predictor, levels, method, 'quant', 'exp', exp, quant.d_quantise, runs)
+def _parts_quant(h, predictor, levels, method, exp, runs=False, tk=None):
+    return _parts_quantised(h, predictor, levels, method, 'quant', 'exp', exp, quant.d_quantise, runs, tk)
 
 
-def _parts_prec(h, predictor, levels, method, bits, runs=False):
-    return _parts_quantised(h, predictor, levels, method, 'prec', 'bits', bits, quant.d_quantise_rel, runs)
+def _parts_prec(h, predictor, levels, method, bits, runs=False, tk=None):
+    return _parts_quantised(h, predictor, levels, method, 'prec', 'bits', bits, quant.d_quantise_rel, runs, tk)
 
 
-def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0, runs=False):
+def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp, t0, runs=False, tk=None):
     """:func:`compress` with ``abs_error``: the quantiser, the lossless pyramid of its integers, the
     bound's check, the version-5 file."""
-    p = _parts_quant(h, predictor, levels, method, exp, runs)
+    p = _parts_quant(h, predictor, levels, method, exp, runs, tk)
     n, E = p['n'], p['E']
     eps = quant.effective(abs_error)
     worst = _quant_max_error(h, n, exp, p['exc'])
@@ -797,11 +910,13 @@ def _compress_quant(path, h, predictor, levels, method, tile_crc, abs_error, exp
         raise RuntimeError(f'error-bounded encode broke its bound: max |restored - highres| = {worst} > {eps} '
                            f'(abs_error = {abs_error}); nothing written to {path}')
     blob, total, crc, table = _bundle(p['x'], p['arrays'], (), method, tile_crc)
-    nbytes = _write(path, p['meta'], blob, total, crc, t0, table, VERSION_RUNS if p['R'] else VERSION_QUANT)
+    nbytes = _write(path, p['meta'], blob, total, crc, t0, table,
+                    _versioned(p['meta'], VERSION_RUNS if p['R'] else VERSION_QUANT))
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
             'levels': p['levels'], 'abs_error': eps, 'abs_error_asked': float(abs_error), 'max_abs_error': worst,
             'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype], **({'exception_runs': p['R']} if runs else {}),
+            **_temporal_result(tk),
             **_quality(_restored_record(h, n, lambda s: quant.d_code(_lib_decode, n.dtype, exp, s), p['exc']), h.dtype)}
 
 
@@ -822,10 +937,10 @@ def _prec_max_error(h, n, bits, exceptions):
     return float(worst.item())
 
 
-def _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0, runs=False):
+def _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits, t0, runs=False, tk=None):
     """:func:`compress` with ``rel_error``: the mantissa quantiser, the lossless pyramid of its integers,
     the guarantee's check, the version-6 file."""
-    p = _parts_prec(h, predictor, levels, method, bits, runs)
+    p = _parts_prec(h, predictor, levels, method, bits, runs, tk)
     n, E = p['n'], p['E']
     eps = quant.effective_rel(rel_error)
     worst = _prec_max_error(h, n, bits, p['exc'])
@@ -833,61 +948,65 @@ def _compress_prec(path, h, predictor, levels, method, tile_crc, rel_error, bits
         raise RuntimeError(f'relative-error encode broke its bound: max |restored - highres| / max(|highres|, 2^-126) '
                            f'= {worst} > {eps} (rel_error = {rel_error}); nothing written to {path}')
     blob, total, crc, table = _bundle(p['x'], p['arrays'], (), method, tile_crc)
-    nbytes = _write(path, p['meta'], blob, total, crc, t0, table, VERSION_RUNS if p['R'] else VERSION_PREC)
+    nbytes = _write(path, p['meta'], blob, total, crc, t0, table,
+                    _versioned(p['meta'], VERSION_RUNS if p['R'] else VERSION_PREC))
     raw = h.numel() * h.element_size()
     return {'bytes': nbytes, 'raw_bytes': raw, 'ratio': raw / nbytes, 'bits_per_sample': 8.0 * nbytes / h.numel(),
             'levels': p['levels'], 'rel_error': eps, 'rel_error_asked': float(rel_error), 'max_rel_error': worst,
             'exceptions': E, 'quant_dtype': _NP_NAME[n.dtype], **({'exception_runs': p['R']} if runs else {}),
+            **_temporal_result(tk),
             **_quality(_restored_record(h, n, lambda s: quant.d_code_rel(_lib_decode, n.dtype, bits, s), p['exc']),
                        h.dtype)}
 
 
-def _sized(h, predictor, levels, tile_crc, max_error=0, abs_error=None, rel_error=None, runs=False):
+def _sized(h, predictor, levels, tile_crc, max_error=0, abs_error=None, rel_error=None, runs=False, tk=None):
     """:func:`compressed_size` of the device tensor ``h`` with checked arguments."""
     if max_error:
         p = _parts_near(h, predictor, levels, 'rice', int(max_error))
         own = {'max_error': int(max_error)}
     elif abs_error is not None:
-        p = _parts_quant(h, predictor, levels, 'rice', quant.exponent(abs_error), runs)
+        p = _parts_quant(h, predictor, levels, 'rice', quant.exponent(abs_error), runs, tk)
         own = {'abs_error': quant.effective(abs_error), 'exceptions': p['E'], 'quant_dtype': _NP_NAME[p['n'].dtype],
                **({'exception_runs': p['R']} if runs else {})}
     elif rel_error is not None:
-        p = _parts_prec(h, predictor, levels, 'rice', quant.mantissa_bits(rel_error), runs)
+        p = _parts_prec(h, predictor, levels, 'rice', quant.mantissa_bits(rel_error), runs, tk)
         own = {'rel_error': quant.effective_rel(rel_error), 'exceptions': p['E'], 'quant_dtype': _NP_NAME[p['n'].dtype],
                **({'exception_runs': p['R']} if runs else {})}
     else:
-        p = _parts_lossless(h, predictor, levels, 'rice')
+        p = _parts_lossless(h, predictor, levels, 'rice', tk)
         own = {'max_error': 0}
     arrays = [p['x'], *p['arrays']]
     total = packing.bundle_size(arrays)
     tiles = packing._rice_enc_plan(arrays, ())['T'] if tile_crc else None  # the table's entries, as _bundle counts them
     return {'bound_bytes': _bound_bytes(p['meta'], total, tiles), 'bundle_bytes': total,
-            'raw_bytes': h.numel() * h.element_size(), 'levels': p['levels'], **own}
+            'raw_bytes': h.numel() * h.element_size(), 'levels': p['levels'], **own, **_temporal_result(tk)}
 
 
 def compressed_size(highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None,
-                    rel_error=None, exceptions='list'):
+                    rel_error=None, exceptions='list', temporal=None, key_interval=None):
     """The size of the file :func:`compress` would write for the same arguments, without writing it:
     the same argument checks, the same quantiser and pyramid (or closed loop), then the measuring
     launches of the Rice bundle (``packing.bundle_size``: the arrays are read once, no bundle is
     allocated, 8 bytes come back).  Returns ``{'bound_bytes', 'bundle_bytes', 'raw_bytes', 'levels'}`` and
     the mode's own entries (``'max_error'``; ``'abs_error'`` or ``'rel_error'`` -- the effective bound --
     with ``'exceptions'`` and ``'quant_dtype'``, and ``'exception_runs'`` under ``exceptions='runs'``, the
-    keyword of :func:`compress`).  ``bundle_bytes`` is exact.  ``bound_bytes`` is the
+    keyword of :func:`compress`; ``'temporal'`` and ``'key_interval'`` under ``temporal='delta'``, the keywords
+    of :func:`compress`).  ``bundle_bytes`` is exact.  ``bound_bytes`` is the
     file's length with the metadata's ``crc32`` at its widest, 4294967295 (the CRC is stored as a
     decimal and is not known before the bytes exist): the file written is never larger and at most 16
     bytes smaller.  The bound itself is not checked here (:func:`compress` checks it before it writes).
     ``method='planes'`` raises ValueError: only Rice bundles are sized on the device."""
     _check_bounds(highres, max_error, abs_error, rel_error)  # before the device is touched
     runs = _check_exceptions(exceptions, abs_error, rel_error)
+    tk = _check_temporal_args(highres, temporal, key_interval, max_error, abs_error, rel_error)
     packing._check_method(method)
     if method != 'rice':
         raise ValueError("compressed_size needs method='rice' (only Rice bundles are sized on the device)")
     h, _ = dev.to_device(highres)
-    return _sized(h, predictor, levels, tile_crc, max_error, abs_error, rel_error, runs)
+    return _sized(h, predictor, levels, tile_crc, max_error, abs_error, rel_error, runs, _single_frame(tk, h))
 
 
-def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0, runs=False):
+def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0, runs=False, tk=None):
     """:func:`compress` with ``target_bits`` / ``target_ratio``: the ladder of ``mode``, the search over
     it with :func:`compressed_size` as the size of a rung, then the chosen rung written by the
     explicit-bound path (which still checks its bound before it writes)."""
@@ -904,7 +1023,7 @@ def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, ta
 
     def size(r):
         key, value = rate.bound_of(mode, ladder[r])
-        return _sized(h, predictor, levels, tile_crc, runs=runs, **{key: value})['bound_bytes']
+        return _sized(h, predictor, levels, tile_crc, runs=runs, tk=tk, **{key: value})['bound_bytes']
     try:
         r, probes = rate.search(size, len(ladder), budget)
     except rate.Unreachable as e:
@@ -912,17 +1031,17 @@ def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, ta
                          f'ladder has bound_bytes = {e.coarsest}; nothing written') from None
     key, value = rate.bound_of(mode, ladder[r])
     if mode == 'abs':
-        out = _compress_quant(path, h, predictor, levels, 'rice', tile_crc, value, ladder[r], t0, runs)
+        out = _compress_quant(path, h, predictor, levels, 'rice', tile_crc, value, ladder[r], t0, runs, tk)
     elif mode == 'rel':
-        out = _compress_prec(path, h, predictor, levels, 'rice', tile_crc, value, ladder[r], t0, runs)
+        out = _compress_prec(path, h, predictor, levels, 'rice', tile_crc, value, ladder[r], t0, runs, tk)
     elif value:
         out = _compress_near(path, h, predictor, levels, 'rice', tile_crc, value, t0)
     else:  # rung 0 of the 'near' ladder is the lossless file
-        out = _compress_lossless(path, h, predictor, levels, 'rice', tile_crc, t0)
+        out = _compress_lossless(path, h, predictor, levels, 'rice', tile_crc, t0, tk)
     return dict(out, target_bytes=budget, bound_bytes=dict(probes)[r], probes=[(ladder[q], b) for q, b in probes])
 
 
-def _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, target, t0, runs=False):
+def _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, target, t0, runs=False, tk=None):
     """:func:`compress` with ``target_psnr``: the ladder of ``mode``, ``rate.search_quality`` over it with the
     PSNR of a rung measured on the device -- float32: the quantiser, then restore and compare in slabs;
     integer samples: the closed loop's restored array against the input -- then the chosen rung written
@@ -956,13 +1075,13 @@ def _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, target, t
                          f'reaches {e.finest} dB; nothing written') from None
     key, value = rate.bound_of(mode, ladder[r])
     if mode == 'abs':
-        out = _compress_quant(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0, runs)
+        out = _compress_quant(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0, runs, tk)
     elif mode == 'rel':
-        out = _compress_prec(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0, runs)
+        out = _compress_prec(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0, runs, tk)
     elif value:
         out = _compress_near(path, h, predictor, levels, method, tile_crc, value, t0)
     else:  # rung 0 of the 'near' ladder is the lossless file
-        out = _compress_lossless(path, h, predictor, levels, method, tile_crc, t0)
+        out = _compress_lossless(path, h, predictor, levels, method, tile_crc, t0, tk)
     return dict(out, target_psnr=target, probes=[(ladder[q], v) for q, v in probes])
 
 
@@ -1047,6 +1166,9 @@ def decompress(path, predictor=None, as_numpy=True):
             if len(arrays) < k:
                 raise ValueError(f'{path}: the exception arrays are missing from the bundle')
             arrays, extra = arrays[:-k], arrays[-k:]
+    tk = _temporal(meta)
+    if tk is not None and lowres.dtype != tk[1]:
+        raise ValueError(f'{path}: the bundle holds {lowres.dtype} samples, the metadata says deltas of {tk[1]}')
     pred = _decode_predictor(path, meta, predictor, lowres.dtype)
     ndim, padding = meta['ndim'], meta['padding']
     nmaps = _nd.NMAPS[ndim]
@@ -1066,6 +1188,10 @@ def decompress(path, predictor=None, as_numpy=True):
         else:
             out = _nd.decode(pred, dec_fn, x, (maps, dims), padding, ndim)
         x = out
+    if tk is not None:  # a time series: the chain of DECODE launches, in place, then the samples' own dtype
+        x = delta.d_decode(x, tk[0], out=x)
+        if q is None:
+            x = x.view(delta.NAMES[meta['sample_dtype']])
     if q is not None and extra is not None and _runs(meta):  # one dequantising launch, then one RUNS launch
         table = _quant_runs(path, extra, _runs(meta), x.numel())
         x = quant.d_patch_runs(q[3](x, q[0], None), table)
@@ -1116,7 +1242,8 @@ def info(path):
     """What a file holds, from its header and metadata alone (no payload read, no GPU):
     ``{'shape', 'sample_dtype', 'ndim', 'levels', 'padding', 'predictor', 'method', 'version',
     'file_bytes', 'bundle_bytes'}`` -- ``shape`` is the array :func:`decompress` returns, the one a
-    :func:`read_region` selection indexes."""
+    :func:`read_region` selection indexes.  A time series also reports ``'temporal'`` (``'delta'``) and
+    ``'key_interval'`` (None: frame 0 alone is a key frame)."""
     with open(path, 'rb') as f:
         version, meta, mlen, n = _read_head(f, path)
         size = os.fstat(f.fileno()).st_size
@@ -1133,6 +1260,8 @@ def info(path):
             param, qdt, E, _ = _quant(meta)
             out.update(quant_dtype=_NP_NAME[qdt], exceptions=E, **({'exception_runs': _runs(meta)} if _runs(meta) else {}),
                        **({'rel_error': 2.0 ** -(param + 1)} if 'prec' in meta else {'abs_error': 2.0 ** (param - 1)}))
+        if _temporal(meta) is not None:  # only a time series reports its coding along the batch axis
+            out.update(temporal='delta', key_interval=_temporal(meta)[0])
         trailer = _tile_crc_trailer(meta, n, size - (_HEAD.size + mlen), path)
         if trailer is not None:  # only a file that has a table reports one
             out['tile_crc'] = trailer[1]
@@ -1288,7 +1417,11 @@ def plan_region(meta, planes=None, batch=None, rows=None, cols=None, level=0):
     batch item when only the first axis is restricted, one per batch item and plane (a row run) where
     rows are cropped; an error-bounded file with exceptions has three more entries behind the maps, its
     exception arrays, each read whole --, 'tiles_decoded': tiles the launches decode, counted per range,
-    'tiles_total': tiles in the file}``."""
+    'tiles_total': tiles in the file}``.
+
+    A time series (``'temporal'`` in the metadata) with ``batch = (a, b)`` is planned for the
+    frames ``[a - a % K, b)`` -- ``[0, b)`` when only frame 0 is a key frame --, the chain the frames asked for
+    are summed along: ``'batch'`` is that range and ``'frames'`` (in such a plan only) the ``(a, b)`` returned."""
     ndim, p = int(meta['ndim']), int(meta['padding'])
     shapes = _meta_shapes(meta)
     nlev = len(shapes)
@@ -1296,7 +1429,10 @@ def plan_region(meta, planes=None, batch=None, rows=None, cols=None, level=0):
     _refuse_image_planes(ndim, planes)
     level = _check_level(level, nlev)
     top = shapes[level][0] if level < nlev else shapes[-1][1]
-    b0, b1 = _clamp_range(batch, top[0], 'batch')
+    b0, b1 = asked = _clamp_range(batch, top[0], 'batch')
+    tk = _temporal(meta)
+    if tk is not None:  # a time series: the chain starts at the key frame at or before the first frame asked for
+        b0 -= b0 % tk[0] if tk[0] else b0
     box = _selection(ndim, top, planes, rows, cols)
     bsel = b1 - b0
     ncrop = ndim - 1  # the leading spatial axes local arrays are cropped along
@@ -1372,7 +1508,8 @@ def plan_region(meta, planes=None, batch=None, rows=None, cols=None, level=0):
                 'ranges': [(0, E, 0)]} for E in _exception_arrays(meta)]
     for i, e in enumerate(arrays):
         e['index'] = i
-    return {'batch': (b0, b1), 'planes': box[0], 'rows': box[ndim - 2], 'cols': box[ndim - 1], 'box': tuple(box),
+    return {'batch': (b0, b1), **({} if tk is None else {'frames': asked}),
+            'planes': box[0], 'rows': box[ndim - 2], 'cols': box[ndim - 1], 'box': tuple(box),
             'level': level, 'levels': levels, 'lowres': lowres_axes[0], 'lowres_axes': lowres_axes, 'arrays': arrays,
             'tiles_decoded': sum((e - 1) // _TILE - f // _TILE + 1 for ar in arrays for f, e, _ in ar['ranges']),
             'tiles_total': sum(_tiles(dev.prod(ar['shape'])) for ar in arrays)}
@@ -1541,7 +1678,9 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
     range is in level-``k`` coordinates; the arrays of finer levels are neither read nor decoded, and
     ``level=L`` (the stored coarsest lowres) runs no codec kernel.  Ranges are clamped; an empty one
     raises ValueError, and so does a ``level`` outside ``[0, L]``.  ``predictor`` as for
-    :func:`decompress`.
+    :func:`decompress`.  A time series (``temporal='delta'``) reads the same box of the frames from the key
+    frame at or before ``b0`` (frame 0 without a ``key_interval``), sums along the chain and returns
+    ``b0 .. b1``.
 
     What a range saves: planes and (for a volume whose planes exceed one tile, ``plan_region``) rows
     crop the arrays read and decoded; a column range does not -- rows are the format's contiguous
@@ -1614,6 +1753,9 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
         q = _quant(meta)
         if q is not None and dtype != q[1]:
             raise ValueError(f'{path}: the bundle holds {dtype} samples, the metadata says {q[1]}')
+        tk = _temporal(meta)
+        if tk is not None and dtype != tk[1]:
+            raise ValueError(f'{path}: the bundle holds {dtype} samples, the metadata says deltas of {tk[1]}')
         nexc = len(_exception_arrays(meta))
         if q is not None and q[2] and any(dev.CODE_TO_TORCH[c] != torch.uint32 for c in rplan['codes'][-nexc:]):
             raise ValueError(f'{path}: the exception arrays of the bundle are not uint32')
@@ -1673,6 +1815,12 @@ def read_region(path, planes=None, batch=None, predictor=None, as_numpy=True, ve
             x = x.contiguous()
     if not plan['levels']:  # the stored coarsest lowres itself
         x = x[(slice(None), *[slice(s - lo, e - lo) for (s, e), (lo, _) in zip(plan['box'], plan['lowres_axes'])])]
+    if tk is not None:  # a time series: the chain from its key frame, in place, then the frames asked for
+        x = x.contiguous()
+        x = delta.d_decode(x, tk[0], out=x)[plan['frames'][0] - plan['batch'][0]:]
+        plan = dict(plan, batch=plan['frames'])
+        if q is None:
+            x = x.view(delta.NAMES[meta['sample_dtype']])
     if q is not None:
         x = _region_restore(meta, plan, x.contiguous(), local[-nexc:] if q[2] else None)
     elif meta.get('sample_dtype') == 'float32':

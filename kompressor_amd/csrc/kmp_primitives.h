@@ -138,4 +138,10 @@ int launch_fill(int dtype, const void* x, int64_t n, void* out, void* ws, hipStr
 // One launch, named "runs".
 int launch_runs(const void* table, int64_t R, void* out, hipStream_t stream);
 
+// kmp_delta.hip: out = x - pred (KMP_ENCODE) or x + pred (KMP_DECODE) modulo 2^(8 width) over n >= 1 samples of
+// ``width`` bytes (KMP_CODER_DELTA; ``out`` may be ``x``).  One launch, named "delta"; KMP_ERR_ARG for
+// another width.
+int launch_delta(int direction, int width, const void* pred, const void* x, int64_t n, void* out,
+                 hipStream_t stream);
+
 }  // namespace kmp

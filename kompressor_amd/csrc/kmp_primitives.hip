@@ -820,6 +820,24 @@ int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* p
                 "runs: a 16-byte aligned table and a 4-byte aligned array");
     return launch_runs(x, n, out, (hipStream_t)stream);
   }
+  if (coder >= 0 && coder_code(coder) == KMP_CODER_DELTA) {
+    // x - pred / x + pred modulo 2^W of two integer arrays of one dtype (kmp_delta.hip)
+    KMP_REQUIRE(pred, "delta: pred is the other array (must not be NULL)");
+    KMP_REQUIRE((coder >> 8) == 0, "delta: the code carries no field");
+    KMP_REQUIRE(pred_dtype == x_dtype, "delta: both arrays in one dtype");
+    KMP_REQUIRE(x_dtype == KMP_U8 || x_dtype == KMP_I8 || x_dtype == KMP_U16 || x_dtype == KMP_I16 || x_dtype == KMP_I32,
+                "delta takes uint8, int8, uint16, int16 or int32 samples");
+    if (n == 0) return KMP_OK;
+    KMP_REQUIRE(x && out, "null pointer");
+    const int64_t w = (int64_t)dtype_size(x_dtype);
+    KMP_REQUIRE((((uintptr_t)pred | (uintptr_t)x | (uintptr_t)out) & (uintptr_t)(w - 1)) == 0,
+                "delta: arrays aligned to their dtype");
+    KMP_REQUIRE(n <= INT64_MAX / 8, "delta: count too large");
+    const uintptr_t nb = (uintptr_t)(n * w), xa = (uintptr_t)x, pa = (uintptr_t)pred, oa = (uintptr_t)out;
+    KMP_REQUIRE(x == out || xa + nb <= oa || oa + nb <= xa, "delta: x and out overlap in part");
+    KMP_REQUIRE(pa + nb <= oa || oa + nb <= pa, "delta: pred and out overlap");
+    return launch_delta(direction, (int)w, pred, x, n, out, (hipStream_t)stream);
+  }
   if (coder >= 0 && is_quant_code(coder_code(coder))) {
     // float32 <-> int16 / int32 on a power-of-two step: no prediction, so none may be passed
     const int code = coder_code(coder);

@@ -727,6 +727,43 @@ def main():
             print(json.dumps(line), flush=True)
         del routes, masks, f32
 
+    # Time series (only with --rows delta): kmp_code with KMP_CODER_DELTA on 512 frames of 64^3 int16
+    # and int32 -- the encode's one launch over the frames 1 .. 511 (two arrays read, one written: 1.5 copies
+    # expected) and the decode's chain of 511 launches of one frame each, in place -- against a device copy of
+    # the same bytes (read once, written once), alternated in one process, 9 samples of --reps calls.
+    if 'delta' in want:
+        from kompressor_amd import delta
+        gen = torch.Generator(device='cuda').manual_seed(0)
+        routes, moved, what = {}, {}, {}
+        for tdt in (torch.int16, torch.int32):
+            tname = 'int16' if tdt == torch.int16 else 'int32'
+            n = torch.randint(-3000, 3000, (512, 64, 64, 64, 1), device='cuda', generator=gen).to(tdt)
+            d, back = torch.empty_like(n), torch.empty_like(n)
+            nbytes = (n.numel() - n[0].numel()) * n.element_size()  # the frames 1 .. 511
+            src = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
+            dst = torch.empty_like(src)
+            assert torch.equal(delta.d_decode(delta.d_encode(n), out=back), n)
+            d.copy_(delta.d_encode(n))
+            tag = f'delta:{tname}'
+            routes[tag] = {'encode': lambda n=n, d=d: delta._launch(kom._lib.ENCODE, n[:-1], n[1:], d[1:]),
+                           'decode_chain': lambda d=d, back=back: delta.d_decode(d, out=back),
+                           'copy': lambda src=src, dst=dst: dst.copy_(src)}
+            moved[tag], what[tag] = 3 * nbytes, f'512 x 64^3 {tname}, frames 1 .. 511'
+        samples = {(t, r): [] for t in routes for r in routes[t]}
+        for _ in range(9):
+            for t in routes:
+                for r in routes[t]:
+                    samples[(t, r)].append(gpu_time(routes[t][r], args.reps))
+        med = {k: float(np.median(v)) for k, v in samples.items()}
+        for (t, r), v in samples.items():
+            line = {'row': f'{t}:{r}', 'what': what[t], 'us': round(med[(t, r)] * 1e6, 1),
+                    'us_min': round(min(v) * 1e6, 1), 'us_max': round(max(v) * 1e6, 1), 'samples': len(v),
+                    'ratio_to_copy': round(med[(t, r)] / med[(t, 'copy')], 4)}
+            if r == 'encode':
+                line['TBps'] = round(moved[t] / med[(t, r)] / 1e12, 3)
+            print(json.dumps(line), flush=True)
+        del routes
+
     # The comparing call (only with --rows compare): kmp_code with KMP_CODER_COMPARE on a 512^3
     # float32 field and on 512 x 64^3 uint16 tiles against the torch composition the bound checks run for
     # the same arrays (container._quant_max_error / near.d_max_abs_error without their restoring launch),
