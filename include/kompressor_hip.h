@@ -155,7 +155,41 @@ typedef enum {
      count), a non-zero field above the low byte, differing or other dtypes, a direction other than
      KMP_ENCODE / KMP_DECODE, arrays not aligned to their dtype, a refused overlap, or this code on any
      other entry point.  n == 0 is KMP_OK and touches nothing.  kmp_last_launch() names it "delta". */
-  KMP_CODER_DELTA = 13
+  KMP_CODER_DELTA = 13,
+  /* Structural similarity of a restored array against its original (kmp_code alone, KMP_ENCODE alone;
+     DESIGN.md §23).  It codes nothing: ``x`` is the original, ``pred`` the restored array (non-NULL), both of
+     ``x_dtype`` == ``pred_dtype``, one of KMP_F32, KMP_U8, KMP_U16, KMP_I8, KMP_I16; n = N D H W samples, N items of
+     D x H x W (D == 1: images); ``out`` an 8-byte aligned device buffer of KMP_SSIM_BYTES.  kmp_code carries one
+     count, so the geometry travels in ``out``: before the call ``out + 64`` holds the REQUEST, eight 64-bit words
+     that the kernels only read:
+       0, 1, 2  D, H, W (int64)       3, 4  C1, C2 (f64 bits)       5  base (f64 bits)       6, 7  0
+     Windows: side 7, uniform weights, NP = 49 samples (D == 1) or 343; only the windows that lie wholly inside
+     one item are counted, (D - 6)(H - 6)(W - 6) per item ((H - 6)(W - 6) for images), no padding.  Samples:
+     integers enter as unsigned (int8 / int16 through v ^ signbit), float32 as (double)v - base; a float32
+     window is SKIPPED iff one of its NP positions holds a non-finite x or r.  Per counted window, with Sx, Sr,
+     Sxx, Srr, Sxr the sums of x, r, x^2, r^2, x r over its samples (exact for integers), in float64:
+       mx = Sx / NP, mr = Sr / NP, vx = (NP Sxx - Sx^2) / (NP (NP - 1)), vr, vxr alike,
+       s = ((2 mx mr + C1)(2 vxr + C2)) / ((mx^2 + mr^2 + C1)(vx + vr + C2)).
+     A RECORD is eight 64-bit words:
+       0  windows counted (u64)             1  windows skipped (u64)
+       2  sum of s over the counted windows (f64 bits)
+       3  their minimum (f64 bits; +inf when there are none)
+       4  status: 0, or 1 for a malformed request, with nothing counted
+       5, 6, 7  0
+     After the call ``out + 0`` holds the record and ``out + 64 (2 + g)`` the partial record of workgroup g for the
+     min(KMP_SSIM_GROUPS, ceil(n / (KMP_SSIM_TILE_H KMP_SSIM_TILE_W))) workgroups that ran; the request and the rest
+     of ``out`` are untouched.  A workgroup owns KMP_SSIM_TILE_H x KMP_SSIM_TILE_W window origins of one item over
+     KMP_SSIM_TILE_D origins along D.  The kernel checks the request: D == 1 or D >= 7; H, W >= 7; D H W divides n
+     (without overflow); C1, C2 finite and > 0; base finite -- a request that fails gives status 1 and zero
+     counts, and no sample is read.  Both arrays 16-byte aligned and W a multiple of 16 / sizeof(sample):
+     16-byte reads; anything else: element reads.  Every window's moments are sums of its own terms in one
+     fixed grouping, the windows are summed in a fixed tree (lanes, waves, workgroups in index order): the
+     same buffers and count give the same 64 bits on every call.  Two launches on ``stream``, no atomics.
+     KMP_ERR_ARG, with nothing launched: a NULL pred (whatever the count), KMP_DECODE, a non-zero field above
+     the low byte, differing or unsupported dtypes, a misaligned ``out``, NULL x or out with n > 0, arrays not
+     aligned to their dtype, or this code on any other entry point.  n == 0 is KMP_OK and touches nothing.  kmp_last_launch() names it
+     "ssim". */
+  KMP_CODER_SSIM = 14
 } kmp_coder;
 #define KMP_CODER_NEAR(code, max_error) ((code) | ((max_error) << 8))
 #define KMP_CODER_QUANT(code, exp) ((code) | (((exp) + 127) << 8))
@@ -167,6 +201,11 @@ typedef enum {
 #define KMP_FILL_GROUPS 1024
 #define KMP_FILL_BYTES (16 * KMP_FILL_GROUPS)
 #define KMP_RUNS_PIECE 256
+#define KMP_SSIM_GROUPS 1024
+#define KMP_SSIM_BYTES (64 * (2 + KMP_SSIM_GROUPS))
+#define KMP_SSIM_TILE_D 32
+#define KMP_SSIM_TILE_H 16
+#define KMP_SSIM_TILE_W 16
 typedef enum { KMP_ENCODE = 0, KMP_DECODE = 1 } kmp_direction;
 
 typedef enum {
@@ -382,7 +421,9 @@ int kmp_tiles(int32_t nsp, int32_t dtype, int32_t direction, const void* src, co
    KMP_FILL_BYTES of scratch; ENCODE alone.  KMP_CODER_RUNS (see kmp_coder): ``x`` the run table (n records),
    ``out`` the float32 array patched in place, ``pred`` NULL; DECODE alone.
    KMP_CODER_DELTA (see kmp_coder): ``x`` and ``pred`` two integer arrays of one dtype, ``out`` their
-   difference (ENCODE) or sum (DECODE) modulo 2^W in that dtype. */
+   difference (ENCODE) or sum (DECODE) modulo 2^W in that dtype.
+   KMP_CODER_SSIM (see kmp_coder): ``x`` the original, ``pred`` the restored array of the same dtype, ``out`` the
+   KMP_SSIM_BYTES that hold the request on entry and the record after; ENCODE alone. */
 int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* pred, int32_t x_dtype,
              const void* x, int64_t n, void* out, kmp_stream_t stream);
 

@@ -90,6 +90,19 @@ def fill_span(n):
 # arrays of one integer dtype (U8, I8, U16, I16, I32); ``out`` may be ``x``
 CODER_DELTA = 13
 
+# structural similarity of a restored array against its original (kmp_code alone, ENCODE alone):
+# ``out`` is SSIM_BYTES -- the record, the request (D, H, W, C1, C2, base) the caller writes, then SSIM_GROUPS
+# partial records; a workgroup owns SSIM_TILE_H x SSIM_TILE_W window origins over SSIM_TILE_D origins along D
+CODER_SSIM = 14
+SSIM_GROUPS = 1024
+SSIM_BYTES = 64 * (2 + SSIM_GROUPS)
+SSIM_TILE_D, SSIM_TILE_H, SSIM_TILE_W = 32, 16, 16
+
+
+def ssim_groups(n):
+    """The workgroups that run for ``n`` samples (each leaves a partial record): a function of ``n`` alone."""
+    return min(SSIM_GROUPS, -(-int(n) // (SSIM_TILE_H * SSIM_TILE_W)))
+
 
 def coder_code(coder):
     return int(coder) & 0xff

@@ -661,7 +661,7 @@ def _single_frame(tk, h):
 
 def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=False, max_error=0, abs_error=None,
              rel_error=None, target_bits=None, target_ratio=None, target_mode=None, target_psnr=None, exceptions='list',
-             temporal=None, key_interval=None):
+             temporal=None, key_interval=None, target_ssim=None):
     """Encode ``highres`` with a built-in ``predictor`` (:class:`MeanPredictor` /
     :class:`LinearPredictor`) and the lossless coder of its dtype (uint8 / uint16 modular, int8 / int16
     modular on the sign-mapped samples, int32 raw, float32 bit-cast to uint32 modulo 2^32) as a ``levels``-deep pyramid -- each level is the
@@ -703,6 +703,17 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
     The chosen rung is written by the explicit-bound path, so the file is byte for byte that call's and
     the result is that call's plus ``'target_psnr'`` and ``'probes'`` (``[(e or m or d, psnr), ...]`` in the
     order asked).  A target above the finest rung's PSNR raises ValueError and writes nothing.
+    ``target_ssim`` (``0 < s <= 1``; alone of the targets and bounds, any ``method``): a structural quality target
+     -- the COARSEST bound of the same ladders whose mean SSIM (``metrics.ssim``: 7-sample windows
+    inside each item, the default peak, float32 samples shifted by the smallest finite value) is at least the
+    target.  Peak, base and the ladder are fixed once from one comparison of the array with itself.  A float32
+    probe is the quantiser, the WHOLE array restored with its exceptions put back (one more array of device
+    memory than ``target_psnr``'s slabs: a window spans slabs) and one SSIM call; a ``'near'`` probe is the closed
+    loop and one SSIM call, and the lossless rung 0 is 1.0 without a launch.  The chosen rung is written by the
+    explicit-bound path, so the file is byte for byte that call's (no new version, no new metadata) and the
+    result is that call's plus ``'ssim'`` (the chosen rung's), ``'target_ssim'`` and ``'probes'`` (``[(e or m or d,
+    ssim), ...]``).  A target above the finest rung's SSIM raises ValueError and writes nothing; so do a
+    spatial extent below 7 (before the device is touched) and a float32 array whose finite values span no range.
     Quality figures: every lossy result also holds ``'mse'``, ``'psnr'`` and ``'value_range'``, measured by
     ``kom.metrics`` on exactly what :func:`decompress` returns (NaNs and infinities, which come back bit for
     bit, are not compared); a lossless one holds ``'mse': 0.0`` and ``'psnr': inf``.
@@ -722,7 +733,9 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
     of frames ``a .. b`` decodes from the key frame at or before ``a``.  The file is version 8 and the result
     also holds ``'temporal'`` and ``'key_interval'``; a single frame writes the ordinary file, byte for byte."""
     mode = rate.check_target(near._input_dtype(highres), target_bits, target_ratio, target_mode, method, max_error,
-                             abs_error, rel_error, target_psnr)  # before the device is touched
+                             abs_error, rel_error, target_psnr, target_ssim)  # before the device is touched
+    if target_ssim is not None:
+        metrics.ssim_dims(highres.shape, 'compress(target_ssim=...)')  # likewise
     exp, bits = _check_bounds(highres, max_error, abs_error, rel_error)  # before the device is touched
     runs = _check_exceptions(exceptions, abs_error, rel_error, mode)  # before the device is touched
     tk = _check_temporal_args(highres, temporal, key_interval, max_error, abs_error, rel_error, mode)  # likewise
@@ -733,6 +746,8 @@ def compress(path, highres, predictor, levels='auto', method='rice', tile_crc=Fa
     tk = _single_frame(tk, h)
     if target_psnr is not None:
         return _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, float(target_psnr), t0, runs, tk)
+    if target_ssim is not None:
+        return _compress_ssim(path, h, predictor, levels, method, tile_crc, mode, float(target_ssim), t0, runs, tk)
     if mode is not None:
         return _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, target_ratio, t0, runs, tk)
     if max_error:
@@ -1041,6 +1056,25 @@ def _compress_target(path, h, predictor, levels, tile_crc, mode, target_bits, ta
     return dict(out, target_bytes=budget, bound_bytes=dict(probes)[r], probes=[(ladder[q], b) for q, b in probes])
 
 
+def _self_compare(h):
+    """The record of the float32 device tensor ``h`` against itself (one comparing call, one read-back) and the
+    largest finite ``|x|``: the value range, the smallest finite value and the 'abs' ladder's ``M``."""
+    words = metrics.record_words(metrics.d_compare(h.reshape(-1), h.reshape(-1)))
+    return words, (float(np.abs(words.view(np.float64)[4:6]).max()) if words[0] else 0.0)
+
+
+def _write_rung(path, h, predictor, levels, method, tile_crc, mode, rung, t0, runs, tk):
+    """The explicit-bound call that codes ``rung`` of the ladder of ``mode`` (it still checks its bound)."""
+    key, value = rate.bound_of(mode, rung)
+    if mode == 'abs':
+        return _compress_quant(path, h, predictor, levels, method, tile_crc, value, rung, t0, runs, tk)
+    if mode == 'rel':
+        return _compress_prec(path, h, predictor, levels, method, tile_crc, value, rung, t0, runs, tk)
+    if value:
+        return _compress_near(path, h, predictor, levels, method, tile_crc, value, t0)
+    return _compress_lossless(path, h, predictor, levels, method, tile_crc, t0, tk)  # rung 0 of 'near'
+
+
 def _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, target, t0, runs=False, tk=None):
     """:func:`compress` with ``target_psnr``: the ladder of ``mode``, ``rate.search_quality`` over it with the
     PSNR of a rung measured on the device -- float32: the quantiser, then restore and compare in slabs;
@@ -1050,9 +1084,8 @@ def _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, target, t
         ladder, peak = rate.ladder_near(h.dtype), float(2 ** (8 * h.element_size()) - 1)
     else:
         # the range of the finite values and the largest finite |x|: one comparing call of h with itself
-        words = metrics.record_words(metrics.d_compare(h.reshape(-1), h.reshape(-1)))
+        words, M = _self_compare(h)
         peak = metrics.summary(words, h.dtype)['value_range']
-        M = float(np.abs(words.view(np.float64)[4:6]).max()) if words[0] else 0.0
         ladder = rate.ladder_abs(M) if mode == 'abs' else rate.ladder_rel()
 
     def psnr(r):
@@ -1073,16 +1106,56 @@ def _compress_psnr(path, h, predictor, levels, method, tile_crc, mode, target, t
     except rate.Unreachable as e:
         raise ValueError(f'{path}: target_psnr = {target} dB cannot be met: the finest rung of the {mode!r} ladder '
                          f'reaches {e.finest} dB; nothing written') from None
-    key, value = rate.bound_of(mode, ladder[r])
-    if mode == 'abs':
-        out = _compress_quant(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0, runs, tk)
-    elif mode == 'rel':
-        out = _compress_prec(path, h, predictor, levels, method, tile_crc, value, ladder[r], t0, runs, tk)
-    elif value:
-        out = _compress_near(path, h, predictor, levels, method, tile_crc, value, t0)
-    else:  # rung 0 of the 'near' ladder is the lossless file
-        out = _compress_lossless(path, h, predictor, levels, method, tile_crc, t0, tk)
+    out = _write_rung(path, h, predictor, levels, method, tile_crc, mode, ladder[r], t0, runs, tk)
     return dict(out, target_psnr=target, probes=[(ladder[q], v) for q, v in probes])
+
+
+def _restored_whole(n, dequantise, exceptions):
+    """Exactly what :func:`decompress` returns for the quantised ``n``, whole: ``dequantise(n)`` with the
+    exceptions put back (one more array of device memory: a window spans slabs, so nothing is cut)."""
+    r = dequantise(n.reshape(-1))
+    if exceptions is not None:
+        idx, bits = exceptions
+        r.view(torch.int32)[idx] = bits.view(torch.int32)
+    return r.reshape(n.shape)
+
+
+def _compress_ssim(path, h, predictor, levels, method, tile_crc, mode, target, t0, runs=False, tk=None):
+    """:func:`compress` with ``target_ssim``: as :func:`_compress_psnr`, with the mean SSIM of a rung as its
+    quality.  Peak, base and the ladder come from the one comparison of ``h`` with itself.  A float32 probe
+    is the quantiser, the WHOLE array restored with its exceptions put back (one more array of device memory
+    than the PSNR's slabs: a window spans slabs) and one ``metrics.d_ssim`` call; a 'near' probe compares the
+    closed loop's restored array, and the lossless rung 0 is 1.0 without a launch."""
+    dims = metrics.ssim_dims(h.shape, 'compress(target_ssim=...)')[1:]
+    items = metrics._items(h)
+    if mode == 'near':
+        ladder, peak, base = rate.ladder_near(h.dtype), float(2 ** (8 * h.element_size()) - 1), 0.0
+    else:
+        words, M = _self_compare(h)
+        ladder = rate.ladder_abs(M) if mode == 'abs' else rate.ladder_rel()
+        peak, base = metrics._ssim_frame(words, True, None, f'{path}: compress(target_ssim=...)')
+    c1, c2 = metrics.ssim_constants(peak)
+
+    def ssim(r):
+        if mode == 'near':
+            if ladder[r] == 0:
+                return 1.0
+            restored = _parts_near(h, predictor, levels, method, int(ladder[r]))['restored']
+        elif mode == 'abs':
+            n, exc = quant.d_quantise(h, ladder[r])
+            restored = _restored_whole(n, lambda s: quant.d_code(_lib_decode, n.dtype, ladder[r], s), exc)
+        else:
+            n, exc = quant.d_quantise_rel(h, ladder[r])
+            restored = _restored_whole(n, lambda s: quant.d_code_rel(_lib_decode, n.dtype, ladder[r], s), exc)
+        words = metrics.record_words(metrics.d_ssim(items, metrics._items(restored), dims, c1, c2, base))
+        return metrics.ssim_summary(words)['ssim']
+    try:
+        r, probes = rate.search_quality(ssim, len(ladder), target)
+    except rate.Unreachable as e:
+        raise ValueError(f'{path}: target_ssim = {target} cannot be met: the finest rung of the {mode!r} ladder '
+                         f'reaches an SSIM of {e.finest}; nothing written') from None
+    out = _write_rung(path, h, predictor, levels, method, tile_crc, mode, ladder[r], t0, runs, tk)
+    return dict(out, ssim=dict(probes)[r], target_ssim=target, probes=[(ladder[q], v) for q, v in probes])
 
 
 def compare(path, highres, peak=None):
@@ -1100,6 +1173,24 @@ def compare(path, highres, peak=None):
         raise ValueError(f'{path} holds an array of shape {tuple(what["shape"])}, the array passed has {tuple(highres.shape)}')
     metrics.check_pair(highres, highres, 'container.compare')  # a dtype that is not compared (int32, uint32): TypeError
     return metrics.compare(highres, decompress(path, as_numpy=False), peak)
+
+
+def ssim(path, highres, peak=None):
+    """The structural similarity of the file ``path`` to the array ``highres`` it was made from: :func:`decompress`
+    on the device, then ``metrics.ssim`` -- ``{'ssim', 'min_ssim', 'windows', 'skipped', 'peak', 'base'}``.  A shape
+    that is not the file's, a rank other than 4 / 5 or a spatial extent below 7 is ValueError, a dtype that is not
+    the file's (or has no SSIM) TypeError, a bad ``peak`` ValueError: all before the device is touched."""
+    peak = metrics.check_peak(peak)
+    what = info(path)
+    dt = near._input_dtype(highres)
+    name = _NP_NAME.get(dt) if isinstance(dt, torch.dtype) else np.dtype(dt).name
+    if name != what['sample_dtype']:
+        raise TypeError(f'{path} holds {what["sample_dtype"]} samples, the array passed {name}')
+    if tuple(highres.shape) != tuple(what['shape']):
+        raise ValueError(f'{path} holds an array of shape {tuple(what["shape"])}, the array passed has {tuple(highres.shape)}')
+    metrics.check_pair(highres, highres, 'container.ssim')  # a dtype without an SSIM (int32, uint32): TypeError
+    metrics.ssim_dims(highres.shape, 'container.ssim')
+    return metrics.ssim(highres, decompress(path, as_numpy=False), peak)
 
 
 def _quant_exceptions(path, arrays, E, numel):

@@ -130,6 +130,11 @@ int launch_maps_from_cell_means(int nsp, int dtype, const void* cm, int64_t B, c
 // Two launches, named "compare"; KMP_ERR_ARG for a dtype it does not take.
 int launch_compare(int dtype, const void* x, const void* r, int64_t n, void* out, int cont, hipStream_t stream);
 
+// kmp_ssim.hip: the structural similarity of ``r`` against ``x`` (KMP_CODER_SSIM; n >= 1 elements of ``dtype``,
+// ``out`` the 8-byte aligned KMP_SSIM_BYTES whose second 64 bytes hold the request).  Two launches, named
+// "ssim"; KMP_ERR_ARG for a dtype it does not take.
+int launch_ssim(int dtype, const void* x, const void* r, int64_t n, void* out, hipStream_t stream);
+
 // kmp_fill.hip: the hold-fill of the marked int16 / int32 array ``x`` into ``out`` (KMP_CODER_FILL; n >= 1,
 // ``ws`` the 8-byte aligned KMP_FILL_BYTES; ``out`` may be ``x``).  Three launches, named "fill"; KMP_ERR_ARG
 // for another dtype.

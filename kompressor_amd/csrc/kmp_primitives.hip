@@ -793,6 +793,21 @@ int kmp_code(int32_t direction, int32_t coder, int32_t pred_dtype, const void* p
     KMP_REQUIRE(x && out, "null pointer");
     return launch_compare(x_dtype, x, pred, n, out, field, (hipStream_t)stream);
   }
+  if (coder >= 0 && coder_code(coder) == KMP_CODER_SSIM) {
+    // structural similarity (kmp_ssim.hip): x the original, pred the restored array, the request in out
+    KMP_REQUIRE(pred, "ssim: pred is the restored array (must not be NULL)");
+    KMP_REQUIRE(direction == KMP_ENCODE, "ssim: KMP_ENCODE alone");
+    KMP_REQUIRE((coder >> 8) == 0, "ssim: the code carries no field");
+    KMP_REQUIRE(pred_dtype == x_dtype, "ssim: both arrays in one dtype");
+    KMP_REQUIRE(x_dtype == KMP_F32 || x_dtype == KMP_U8 || x_dtype == KMP_U16 || x_dtype == KMP_I8 || x_dtype == KMP_I16,
+                "ssim takes float32, uint8, uint16, int8 or int16 samples");
+    KMP_REQUIRE(((uintptr_t)out & 7) == 0, "ssim: out must be 8-byte aligned");
+    if (n == 0) return KMP_OK;
+    KMP_REQUIRE(x && out, "null pointer");
+    KMP_REQUIRE((((uintptr_t)x | (uintptr_t)pred) & (uintptr_t)(dtype_size(x_dtype) - 1)) == 0,
+                "ssim: arrays aligned to their dtype");
+    return launch_ssim(x_dtype, x, pred, n, out, (hipStream_t)stream);
+  }
   if (coder >= 0 && coder_code(coder) == KMP_CODER_FILL) {
     // hold-fill of a marked integer array (kmp_fill.hip): pred is the scratch
     const int64_t w = x_dtype == KMP_I16 ? 2 : 4;

@@ -14,6 +14,10 @@ else -- ``mse``, ``rmse``, ``psnr``, ``nrmse`` -- is host arithmetic on those wo
 * ``nrmse = rmse / peak`` (``inf`` when ``peak == 0`` and ``rmse > 0``).
 
 The record is deterministic: the same buffers give the same 64-bit words on every call.
+
+Structural similarity: one ``kmp_code`` call with ``KMP_CODER_SSIM`` leaves the count, the sum
+and the minimum of the SSIM index over every 7 x 7 (images) or 7 x 7 x 7 (volumes) window that lies inside one
+item (:func:`ssim`, :func:`d_ssim`, :func:`ssim_summary`).
 """
 
 import math
@@ -137,6 +141,115 @@ def summary(record_words, dtype, peak=None):
 
 def _empty_words():
     return np.array([0, 0, 0, 0, _INF_BITS, _NINF_BITS + (1 << 64), 0, 0], np.uint64)
+
+
+# ---- structural similarity ----
+
+SSIM_WINDOW = 7
+
+
+def ssim_dims(shape, who='metrics.ssim'):
+    """``(N, D, H, W)`` of an array of ``shape`` in the package's layouts ``(B, H, W, C)`` / ``(B, D, H, W, C)``
+    -- ``N = B * C`` items, ``D = 1`` for images.  ValueError for another rank or a spatial extent below 7."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) not in (4, 5):
+        raise ValueError(f'{who}: arrays are (B, H, W, C) or (B, D, H, W, C), got shape {shape}')
+    spatial = shape[1:-1]
+    if min(spatial) < SSIM_WINDOW:
+        raise ValueError(f'{who}: every spatial extent must be at least {SSIM_WINDOW} (the window), got {spatial}')
+    return (shape[0] * shape[-1], 1 if len(spatial) == 2 else spatial[0], spatial[-2], spatial[-1])
+
+
+def ssim_constants(peak):
+    """``(C1, C2) = ((0.01 L)^2, (0.03 L)^2)`` for the peak ``L``."""
+    return (0.01 * peak) ** 2, (0.03 * peak) ** 2
+
+
+def _items(t):
+    """The device tensor ``t`` in one of the package's layouts as contiguous items: channels first."""
+    return t if t.shape[-1] == 1 else t.movedim(-1, 1).contiguous()
+
+
+def d_ssim(x, r, dims, c1, c2, base):
+    """One ``kmp_code`` call with ``KMP_CODER_SSIM`` on two contiguous device tensors of one dtype and size
+    (``x`` the original) holding items of ``dims = (D, H, W)`` samples each: the device buffer of ``SSIM_BYTES``
+    whose first eight 64-bit words are the record."""
+    if x.dtype != r.dtype or x.numel() != r.numel() or x.dtype not in DTYPES:
+        raise TypeError(f'metrics.d_ssim: two tensors of one size and of one of {DTYPES}')
+    D, H, W = (int(d) for d in dims)
+    request = np.zeros(8, np.int64)
+    request[:3] = (D, H, W)
+    request[3:6] = np.array([c1, c2, base], np.float64).view(np.int64)
+    buf = dev.empty((_lib.SSIM_BYTES // 8,), torch.int64)
+    head = np.zeros(16, np.int64)
+    head[3] = _INF_BITS  # the record of nothing counted, for an empty input
+    head[8:] = request
+    buf[:16] = torch.from_numpy(head).to('cuda')
+    check(lib.kmp_code(_lib.ENCODE, _lib.CODER_SSIM, dev.dtype_code(r), r.data_ptr(), dev.dtype_code(x), x.data_ptr(),
+                       x.numel(), buf.data_ptr(), dev.stream()), 'ssim')
+    return buf
+
+
+def ssim_summary(words):
+    """The host arithmetic on an SSIM record's eight 64-bit words: ``{'ssim', 'min_ssim', 'windows', 'skipped'}``
+    -- ``ssim`` the mean over the counted windows, ``nan`` when there are none.  ValueError for a record
+    whose status says the request was malformed."""
+    w = np.ascontiguousarray(np.asarray(words).reshape(-1)[:RECORD_WORDS]).view(np.uint64)
+    f = w.view(np.float64)
+    if int(w[4]) != 0:
+        raise ValueError(f'metrics.ssim_summary: the kernel refused the request (status {int(w[4])})')
+    windows = int(w[0])
+    return {'ssim': float(f[2]) / windows if windows else math.nan, 'min_ssim': float(f[3]), 'windows': windows,
+            'skipped': int(w[1])}
+
+
+def _ssim_frame(words, is_float, peak, who):
+    """``(peak, base)`` of a comparison from the record of the original against itself (``words``; None for
+    integer samples, whose peak is ``2^W - 1`` -- passed in -- and whose base is 0)."""
+    if not is_float:
+        return peak, 0.0
+    f = words.view(np.float64)
+    count = int(words[0])
+    base = float(f[4]) if count else 0.0
+    if peak is None:
+        peak = float(f[5]) - float(f[4]) if count else 0.0
+        if peak == 0:
+            raise ValueError(f'{who}: the finite originals span no range, so there is no default peak and no SSIM')
+    return peak, base
+
+
+def ssim(original, restored, peak=None):
+    """``{'ssim', 'min_ssim', 'windows', 'skipped', 'peak', 'base'}`` of ``restored`` against ``original``: the
+    mean and the minimum of the structural similarity index over every 7 x 7 (``(B, H, W, C)`` arrays) or
+    7 x 7 x 7 (``(B, D, H, W, C)``) window that lies inside one item, uniform weights, sample variances
+    (DESIGN.md §23).  Two numpy arrays or CUDA tensors of one shape and dtype (float32, uint8, uint16, int8,
+    int16); ``C > 1`` channels are ``C`` times the items, through a channel-first copy.  ``peak`` defaults to
+    the range of the finite originals (float32) or ``2^W - 1``; float32 samples enter as ``v - base``, ``base``
+    the smallest finite original, and a window holding a non-finite value on either side is ``skipped``.
+    TypeError for an unsupported dtype or two different ones, ValueError for two shapes, a rank other than
+    4 / 5, a spatial extent below 7 or a bad ``peak`` -- all before the device is touched; a float32 original
+    without a value range and no ``peak`` is ValueError after the one comparison with itself."""
+    t = check_pair(original, restored, 'metrics.ssim')
+    shape = tuple(original.shape) if isinstance(original, torch.Tensor) else np.shape(original)
+    _, D, H, W = ssim_dims(shape)
+    peak = check_peak(peak)
+    x, _ = dev.to_device(original)
+    r, _ = dev.to_device(restored)
+    return _ssim_of(_items(x), _items(r), (D, H, W), t, peak, 'metrics.ssim')
+
+
+def _ssim_of(x, r, dims, t, peak, who):
+    """:func:`ssim` on contiguous device items with checked arguments."""
+    is_float = t == torch.float32
+    if not is_float and peak is None:
+        peak = float(2 ** (8 * t.itemsize) - 1)
+    words = None
+    if is_float:
+        words = record_words(d_compare(x.reshape(-1), x.reshape(-1)))
+    peak, base = _ssim_frame(words, is_float, peak, who)
+    c1, c2 = ssim_constants(peak)
+    out = ssim_summary(record_words(d_ssim(x, r, dims, c1, c2, base)))
+    return dict(out, peak=peak, base=base)
 
 
 def compare(original, restored, peak=None):

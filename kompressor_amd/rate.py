@@ -22,6 +22,7 @@ whose finer neighbour does not (or rung 0), after at most ``2 + ceil(log2 L)`` p
 
 A quality target (``target_psnr``) runs over the same ladders the other way round:
 :func:`search_quality` returns a rung that meets the target whose coarser neighbour does not.
+``target_ssim`` is the same search with the mean SSIM as the quality.
 """
 
 import math
@@ -46,25 +47,28 @@ def _positive_finite(name, v):
 
 
 def check_target(dtype, target_bits, target_ratio, target_mode, method='rice', max_error=0, abs_error=None,
-                 rel_error=None, target_psnr=None):
+                 rel_error=None, target_psnr=None, target_ssim=None):
     """The arguments of a rate- or quality-controlled ``compress``, checked on the host alone.  Returns None
     when no target is given (``target_mode`` must then be None too), else the mode: the dtype's default or
     ``target_mode``.  ValueError: more than one target, a target that is no positive finite number, a
-    target together with a bound, a size target with a method other than 'rice', an unknown mode or one
-    that does not fit the dtype; TypeError: a sample dtype without a lossy mode."""
-    given = [k for k, v in (('target_bits', target_bits), ('target_ratio', target_ratio), ('target_psnr', target_psnr))
-             if v is not None]
+    ``target_ssim`` above 1, a target together with a bound, a size target with a method other than 'rice', an
+    unknown mode or one that does not fit the dtype; TypeError: a sample dtype without a lossy mode."""
+    targets = {'target_bits': target_bits, 'target_ratio': target_ratio, 'target_psnr': target_psnr,
+               'target_ssim': target_ssim}
+    given = [k for k, v in targets.items() if v is not None]
     if not given:
         if target_mode is not None:
             raise ValueError('target_mode needs target_bits, target_ratio or target_psnr')
         return None
     if len(given) > 1:
+        if target_ssim is not None:
+            raise ValueError(f'target_ssim stands alone among the targets, not with {" and ".join(given[:-1])}')
         raise ValueError(f'give one of target_bits, target_ratio and target_psnr, not {" and ".join(given)}')
-    _positive_finite(given[0], {'target_bits': target_bits, 'target_ratio': target_ratio,
-                                'target_psnr': target_psnr}[given[0]])
+    if _positive_finite(given[0], targets[given[0]]) > 1 and target_ssim is not None:
+        raise ValueError(f'target_ssim must lie in (0, 1], got {target_ssim!r}')
     if isinstance(max_error, bool) or max_error != 0 or abs_error is not None or rel_error is not None:
         raise ValueError(f'{given[0]} chooses the bound: not with max_error, abs_error or rel_error')
-    if target_psnr is None and method != 'rice':
+    if target_psnr is None and target_ssim is None and method != 'rice':
         raise ValueError("target_bits / target_ratio need method='rice' (only Rice bundles are sized on the device)")
     try:
         name = near._BY_NAME_INV[near.torch_dtype(dtype)]

@@ -804,6 +804,49 @@ def main():
             print(json.dumps(line), flush=True)
         del xf, rf, ru, routes
 
+    # The SSIM call (only with --rows ssim): kmp_code with KMP_CODER_SSIM on a 512^3 float32 field
+    # and on 512 x 64^3 uint16 tiles, with 7 x 7 x 7 windows (one volume / 512 volumes) and with 7 x 7 windows
+    # (512 images of 512^2 / 32768 of 64^2), against the comparing call on the same buffers, alternated in one
+    # process, 9 samples of --reps calls.  The request is written once: the timed call is the two launches.
+    if 'ssim' in want:
+        from kompressor_amd import _device as dev, metrics
+        gen = torch.Generator(device='cuda').manual_seed(0)
+        xf = torch.randn((512, 512, 512), device='cuda', generator=gen)
+        rf = xf + 2.0 ** -10 * torch.randn((512, 512, 512), device='cuda', generator=gen)
+        xu = vol.reshape(-1)
+        ru = (xu.view(torch.int16).to(torch.int32) & 0xffff).add_(torch.randint(-3, 4, xu.shape, device='cuda',
+                                                                                generator=gen)).clamp_(0, 65535).to(torch.uint16)
+        cbuf = metrics.d_compare(xf.reshape(-1), rf.reshape(-1))
+        lo, hi = float(xf.min().item()), float(xf.max().item())
+
+        def ssim_call(x, r, dims, peak, base):
+            buf = metrics.d_ssim(x, r, dims, *metrics.ssim_constants(peak), base)
+            assert metrics.ssim_summary(metrics.record_words(buf))['windows'] > 0
+            code = dev.dtype_code(x)
+            return lambda: kom._lib.check(kom._lib.lib.kmp_code(kom._lib.ENCODE, kom._lib.CODER_SSIM, code, r.data_ptr(), code,
+                                                                x.data_ptr(), x.numel(), buf.data_ptr(), dev.stream()), 'ssim')
+        xff, rff = xf.reshape(-1), rf.reshape(-1)
+        routes = {'f512_float32': {'compare': lambda: metrics.d_compare(xff, rff, cbuf),
+                                   'ssim3d': ssim_call(xff, rff, (512, 512, 512), hi - lo, lo),
+                                   'ssim2d': ssim_call(xff, rff, (1, 512, 512), hi - lo, lo)},
+                  'c3_uint16': {'compare': lambda: metrics.d_compare(xu, ru, cbuf),
+                                'ssim3d': ssim_call(xu, ru, (64, 64, 64), 65535.0, 0.0),
+                                'ssim2d': ssim_call(xu, ru, (1, 64, 64), 65535.0, 0.0)}}
+        nbytes = {'f512_float32': 2 * xf.numel() * 4, 'c3_uint16': 2 * xu.numel() * 2}
+        samples = {(t, d): [] for t in routes for d in routes[t]}
+        for _ in range(9):
+            for t in routes:
+                for d in routes[t]:
+                    samples[(t, d)].append(gpu_time(routes[t][d], args.reps))
+        med = {k: float(np.median(v)) for k, v in samples.items()}
+        for (t, d), v in samples.items():
+            line = {'row': f'ssim:{t}:{d}', 'what': f'{nbytes[t]} bytes of samples', 'us': round(med[(t, d)] * 1e6, 1),
+                    'TBps_read': round(nbytes[t] / med[(t, d)] / 1e12, 3),
+                    'us_min': round(min(v) * 1e6, 1), 'us_max': round(max(v) * 1e6, 1), 'samples': len(v),
+                    'ratio_to_compare': round(med[(t, d)] / med[(t, 'compare')], 4)}
+            print(json.dumps(line), flush=True)
+        del xf, rf, ru, routes
+
     # geometry primitives (volume/utils.py) on the C3 tile batch
     if not want or 'primitives' in want:
         hp, _ = _nd.d_pad_highres(vol, 3)                       # [512, 65^3]

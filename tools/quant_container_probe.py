@@ -9,7 +9,9 @@ bounds are ``rel_error`` None, 1e-1, 1e-2, 1e-3.  ``--target`` measures rate con
 §19): ``compress(target_bits=4 / 8)`` against ``compress(abs_error=the chosen bound)``, the probes it
 made and the time of one probe.  ``--psnr`` measures quality targets:
 ``compress(target_psnr=60 / 90)`` against ``compress(abs_error=the chosen bound)``, the probes, and the
-time of the quality pass every lossy ``compress`` now holds."""
+time of the quality pass every lossy ``compress`` now holds.  ``--ssim`` measures structural targets (DESIGN.md
+§23): ``compress(target_ssim=0.99)`` against ``compress(abs_error=the chosen bound)``, the probes and the time
+of one probe."""
 import json, os, sys, tempfile
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -102,6 +104,42 @@ if '--psnr' in sys.argv:
                           'probes': len(res['probes']), 'probe_rungs': [p[0] for p in res['probes']],
                           'target_total_ms': stat(rows['target']), 'explicit_total_ms': stat(rows['explicit']),
                           'quality_pass_ms': stat(rows['quality'])}), flush=True)
+    os.remove(path)
+    sys.exit(0)
+if '--ssim' in sys.argv:
+    # structural targets: compress(target_ssim=0.99) against compress(abs_error=chosen) on the same
+    # field, alternated over three timed rounds; the probes it made, and the time of one probe (the quantiser,
+    # the whole array restored, one SSIM call and its read-back; synchronised)
+    import time
+    from kompressor_amd import metrics, quant, _lib
+    path = os.path.join(d, 'v.kmp')
+    rows = {'target': [], 'explicit': [], 'probe': []}
+    for rnd in range(4):
+        res = container.compress(path, xt, pred, levels=3, target_ssim=0.99)
+        tt = dict(container.last_timing)
+        target_bytes = open(path, 'rb').read()
+        ex = container.compress(path, xt, pred, levels=3, abs_error=res['abs_error'])
+        te = dict(container.last_timing)
+        assert open(path, 'rb').read() == target_bytes and res['ssim'] >= 0.99
+        e = quant.exponent(res['abs_error'])
+        frame = metrics.ssim(xt, xt)  # peak and base, outside the timed probe
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        nq, exc = quant.d_quantise(xt, e)
+        r = container._restored_whole(nq, lambda s: quant.d_code(_lib.DECODE, nq.dtype, e, s), exc)
+        words = metrics.record_words(metrics.d_ssim(metrics._items(xt), metrics._items(r), metrics.ssim_dims(xt.shape)[1:],
+                                                    *metrics.ssim_constants(frame['peak']), frame['base']))
+        tp = time.perf_counter() - t0
+        assert metrics.ssim_summary(words)['ssim'] == res['ssim']
+        del nq, r
+        if rnd:
+            rows['target'].append(tt['total']); rows['explicit'].append(te['total']); rows['probe'].append(tp)
+    stat = lambda xs: [round(1e3 * f(xs), 2) for f in (lambda v: float(np.median(v)), min, max)]
+    print(json.dumps({'target_ssim': 0.99, 'abs_error': res['abs_error'], 'ssim': res['ssim'], 'psnr': res['psnr'],
+                      'bits_per_sample': round(res['bits_per_sample'], 4), 'bytes': res['bytes'],
+                      'probes': len(res['probes']), 'probe_rungs': [p[0] for p in res['probes']],
+                      'target_total_ms': stat(rows['target']), 'explicit_total_ms': stat(rows['explicit']),
+                      'one_probe_ms': stat(rows['probe'])}), flush=True)
     os.remove(path)
     sys.exit(0)
 for rnd in range(4):
